@@ -11,7 +11,13 @@ scaling), no data-path collective; barrier + max-over-ranks timing.  Under a lau
 WORLD_SIZE, which must equal --gpus) this process is one rank; `python bench.py --gpus N` with no
 launcher starts the N ranks itself (launch_ranks) before anything touches the GPU.
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+A plain run measures the headline only: set up, warm up, time the K forward steps, print the JSON line.
+--full adds every secondary line (inverse NTT, encode+CRT, recombine, C4 / C5, reference-geometry pipeline,
+other shapes, trace GEMM, U64 path, committed-profile roofline figures, CPU baseline); --only X selects lines of
+the full run and implies it.  --dump-outputs DIR writes a seeded sample of the batch as the last timed forward
+step left it (DIR/*.npy, float64, exact for the 50-bit residues).
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -43,12 +49,17 @@ def parse():
     ap.add_argument("--ntt-chunk", type=int, default=None, help="MFHE_OPT_NTT_CHUNK_BYTES override (tuning)")
     ap.add_argument("--ntt-pack", type=int, default=None, help="MFHE_OPT_NTT_PACK override (tuning)")
     ap.add_argument("--ntt-plan", type=int, default=None, help="MFHE_OPT_NTT_PLAN override (tuning)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary lines (everything but the forward-NTT headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed forward step's output batch to DIR/*.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="skip the reference-geometry pipeline and other-config NTT lines (N=1 only)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-c5", action="store_true", help="skip the BASELINE C5 residue-shard line")
-    ap.add_argument("--only", default="all", help="all | ntt | crt | recombine | c4 | c5 | u64 (profiling)")
+    ap.add_argument("--only", default="all",
+                    help="all | ntt | crt | recombine | c4 | c5 | u64 (profiling; anything but all implies --full)")
     ap.add_argument("--recombine-batch", type=int, default=256,
                     help="polys per step for the residue-shard INTT + CRT recombine line (0 = skip)")
     ap.add_argument("--secondary-timeout", type=float, default=300.0,
@@ -700,6 +711,47 @@ def u64_line(reps=20, warm=3):
     return res
 
 
+def gen_batch(dev, moduli, N, batch, rank=0):
+    """The headline's input: synthetic residues uniform in [0, q_l), generated on device from a fixed seed (the
+    same batch for the same arguments, run after run).  Returns the generator (later lines draw from it) and the
+    flat [batch][L][N] int64 batch."""
+    import torch
+    g = torch.Generator(device=dev).manual_seed(0x4D46484500000000 % (2 ** 63) + 3 + rank)
+    data = torch.empty(batch * len(moduli) * N, dtype=torch.int64, device=dev)
+    qt = torch.tensor(moduli, dtype=torch.int64, device=dev).repeat_interleave(N).repeat(batch)
+    data.random_(0, 2 ** 62, generator=g)
+    data.remainder_(qt)
+    del qt
+    return g, data
+
+
+DUMP_ROWS = 48        # whole transforms kept by --dump-outputs (48 x N x 8 B = 24 MiB at N = 2^16)
+DUMP_ELEMS = 1 << 20    # plus this many single elements from anywhere in the batch (8 MiB)
+
+
+def dump_outputs(path, data, rows, N):
+    """--dump-outputs: the batch as the last timed forward step left it -- what a caller of mfhe_ntt_fwd holds
+    afterwards -- as a fixed, seeded sample (the whole batch is 4 GiB at the default shape), under 64 MB in all:
+      ntt_fwd_rows.npy            [R][N]  R = min(rows, DUMP_ROWS) whole (poly, limb) transforms
+      ntt_fwd_rows_index.npy      [R]     their row numbers (poly * L + limb)
+      ntt_fwd_elements.npy        [E]     E = min(rows * N, DUMP_ELEMS) single elements, spread over every chunk
+      ntt_fwd_elements_index.npy  [E]     their flat indices
+    All float64: residues of 50-bit primes and indices < 2^53 are exact.  The sample depends only on the shape, and
+    the input batch only on the arguments, so two builds can be compared file for file."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(0x4D464845)
+    r_idx = np.sort(rng.choice(rows, size=min(rows, DUMP_ROWS), replace=False))
+    e_idx = np.sort(rng.choice(rows * N, size=min(rows * N, DUMP_ELEMS), replace=False))
+    r = data.view(rows, N)[torch.from_numpy(r_idx).to(data.device)].cpu().numpy()
+    e = data[torch.from_numpy(e_idx).to(data.device)].cpu().numpy()
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in (("ntt_fwd_rows", r), ("ntt_fwd_rows_index", r_idx),
+                    ("ntt_fwd_elements", e), ("ntt_fwd_elements_index", e_idx)):
+        np.save(out / f"{name}.npy", a.astype(np.float64))
+
+
 WATCHDOG_EXIT = 3   # exit status of a run whose secondary lines the watchdog stopped (the headline is printed)
 
 
@@ -776,6 +828,13 @@ def main():
                  f"(n_gpus is reported from the ranks that actually run)")
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    # a plain run times the forward headline and nothing else; the secondary lines belong to --full
+    full = args.full or args.only != "all"
+    only = args.only if full else "headline"
+    if args.dump_outputs and only not in ("headline", "all", "ntt"):
+        sys.exit(f"bench.py: --dump-outputs writes the forward-NTT batch, which --only {only} does not compute")
     import torch
     import torch.distributed as dist
 
@@ -830,13 +889,7 @@ def main():
             ctx.set_option(opt, val)
     stream = torch.cuda.current_stream()
 
-    # synthetic residues uniform in [0, q_l), generated on device
-    g = torch.Generator(device=dev).manual_seed(0x4D46484500000000 % (2 ** 63) + 3 + rank)
-    data = torch.empty(batch * L * N, dtype=torch.int64, device=dev)
-    qt = torch.tensor(moduli, dtype=torch.int64, device=dev).repeat_interleave(N).repeat(batch)
-    data.random_(0, 2 ** 62, generator=g)
-    data.remainder_(qt)
-    del qt
+    g, data = gen_batch(dev, moduli, N, batch, rank)
 
     def barrier():
         if world > 1:
@@ -862,14 +915,17 @@ def main():
         return t.item(), ev_ms / steps
 
     res = {}
-    if args.only in ("all", "ntt"):
+    if only in ("headline", "all", "ntt"):
         wall, ev_ms = timed(lambda: ctx.ntt_fwd(data, batch=batch, stream=stream), args.steps, args.warmup)
         res["fwd_wall"], res["fwd_ev_ms"] = wall, ev_ms
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, data, batch * L, N)   # before anything else touches the batch
+    if only in ("all", "ntt"):
         # the inverse with exactly the forward's steps and warm-up (the first ~30 ms of calls run in the clock
         # ramp, profiles/r02_bench_steps.txt, so fewer steps would understate it)
         wall_i, ev_i = timed(lambda: ctx.ntt_inv(data, batch=batch, stream=stream), args.steps, args.warmup)
         res["inv_ev_ms"], res["inv_wall"] = ev_i, wall_i
-    if args.only in ("all", "crt"):
+    if only in ("all", "crt"):
         # encode+CRT op = one real poly of N coefficients: decompose (f64 -> L residues) + compose (-> f64/delta)
         cb = max(1, batch // 4)
         z = torch.rand(cb * N, dtype=torch.float64, device=dev, generator=g) * 2 - 1
@@ -923,7 +979,9 @@ def main():
                                "algorithmic_bytes_per_launch": alg_bytes,
                                "hbm_read_frac": round(ach / 2 / HBM_PEAK_GBS, 4),
                                "event_ms_per_transform": round(res["fwd_ev_ms"], 4)}
-            out["roofline"].update(profile_figures(N, L, batch, alg_bytes, world))
+            if full:
+                out["roofline"].update(profile_figures(N, L, batch, alg_bytes, world))
+        if "inv_wall" in res:
             out["inverse_NTT_per_s"] = ntts / (res["inv_wall"] / args.steps)
             out["inverse_over_forward"] = round(out["inverse_NTT_per_s"] / out["value"], 4)
         if "crt_ev_ms" in res:
@@ -935,9 +993,15 @@ def main():
     # on more than one real GPU (RCCL communicators of libmfhe beside torch's): a watchdog on every rank bounds
     # them, so a hang there still leaves the headline line printed (rank 0); the stopped run then exits with
     # WATCHDOG_EXIT (3), so the driver sees that the secondary lines did not finish.
+    if not full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     wd = start_watchdog(out, rank, args.secondary_timeout)
 
-    if args.only in ("all", "recombine") and args.recombine_batch and L % world == 0:
+    if only in ("all", "recombine") and args.recombine_batch and L % world == 0:
         try:
             # residue sharding: rank g owns limbs [g*L/G, (g+1)*L/G) of every poly.  One step =
             # forward + inverse NTT of the shard (a computation round trip) + RCCL exchange + sharded CRT

@@ -23,7 +23,7 @@ if [ "${2:-}" = "tests" ]; then
   [ $rc -ne 0 ] && { echo "pytest rc=$rc"; exit $rc; }
 fi
 
-timeout -k 10 400 python bench.py --gpus 1 --steps $STEPS --warmup $WARM > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 400 python bench.py --gpus 1 --steps $STEPS --warmup $WARM --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
     || { echo "bench failed rc=$?"; tail -20 "$OUT/bench.err"; exit 3; }
 python3 -c "import json,sys; d=json.load(open('$OUT/bench.json')); print({k: d[k] for k in ('value', 'ms_per_step')}, d['roofline']['frac'])"
 
