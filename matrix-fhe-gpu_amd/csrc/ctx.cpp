@@ -18,8 +18,8 @@
 #include <vector>
 
 #include "host_math.hpp"
-#include "gemm.hpp"
 #include "mfhe_ctx.hpp"
+#include "wcrt_gemm.hpp"
 
 namespace mfhe {
 
@@ -337,7 +337,7 @@ static int build_wcrt(mfhe_ctx* c) {
             (rc = upload(c, &c->d_wdgp, gp)))
             return rc;
     }
-    // i8 MFMA operand planes (gemm.hip): D balanced base-256 digits of every V / V^-1 entry, and
+    // i8 MFMA operand planes (wcrt_digitize.hpp): D balanced base-256 digits of every V / V^-1 entry, and
     // 256^s mod q for the epilogue.  Needs 2^27 < q (|acc_s| < q) and q < 2^59 (D <= 8).
     bool big = true;
     for (uint64_t q : c->moduli) big = big && q > (1ull << 27);
@@ -350,7 +350,7 @@ static int build_wcrt(mfhe_ctx* c) {
         for (int l = 0; l < L; ++l) {
             int8_t d[8];
             for (size_t e = 0; e < plane; ++e) {
-                // plane layout [k/32][row][k%32] (gemm.hip "k-panel-major"): row = w, k = r of V[w][r]
+                // plane layout [k/32][row][k%32] (wcrt_digitize.hpp "k-panel-major"): row = w, k = r of V[w][r]
                 const size_t w = e / PHI, r = e % PHI, o = ((r >> 5) * PHI + w) * 32 + (r & 31);
                 balanced_digits(V[(size_t)l * plane + e], D, d);
                 for (int i = 0; i < D; ++i) vd[((size_t)l * D + i) * plane + o] = d[i];
@@ -388,7 +388,7 @@ static int build_wcrt(mfhe_ctx* c) {
                 ep[(size_t)l * 8 + 4] = centred(p96, q);
             }
             if ((rc = upload(c, &c->d_wepi, ep))) return rc;
-            // factored forward (gemm.hip, 771 = 3 x 257): zeta = eta^3 of order 257, omega = eta^257 of order 3
+            // factored forward (wcrt_digitize.hpp, 771 = 3 x 257): zeta = eta^3 of order 257, omega = eta^257 of order 3
             if (D <= 6) {
                 constexpr int FK = 256;
                 std::vector<int8_t> zd((size_t)L * D * FK * FK);
@@ -416,7 +416,7 @@ static int build_wcrt(mfhe_ctx* c) {
                         }
                 }
                 if ((rc = upload(c, &c->d_wZdig, zd)) || (rc = upload(c, &c->d_wfold, fo))) return rc;
-                // factored inverse (gemm.hip mfma_digitize_ifold_kernel / epilogue): the 771-point interpolation
+                // factored inverse (wcrt_digitize.hpp mfma_digitize_ifold_kernel / epilogue): the 771-point interpolation
                 // with zeros at the non-units, reduced mod Phi_771 (tools/wcrt_factor_check.py).  Zi[i][k] =
                 // zeta^-((i+1)(k+1)); kappa[a][t] = 771^-1 omega^(-a t); lam1[a][t] = kappa[a][t] - kappa[a][t+1],
                 // lam2[a][t] = kappa[a][t+2] - kappa[a][t+1] (t mod 3); z[l][0 / 1][k] = zeta^(-255 / -256 (k+1)).

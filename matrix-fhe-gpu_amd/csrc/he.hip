@@ -13,9 +13,10 @@
 
 #include <cmath>
 
-#include "gemm.hpp"
+#include "cdft.hpp"
 #include "mfhe_ctx.hpp"
 #include "ring_row.hpp"
+#include "wcrt_gemm.hpp"
 
 extern "C" int mfhe_ntt_fwd(mfhe_ctx*, uint64_t*, size_t, int, int, mfhe_stream_t);
 extern "C" int mfhe_ntt_inv(mfhe_ctx*, uint64_t*, size_t, int, int, mfhe_stream_t);
@@ -108,7 +109,7 @@ __global__ void gaussian_kernel(uint64_t* e, const uint64_t* qmu, int L, int log
 }
 
 // The same draw as gaussian_kernel, once per [w][y][x] as a centred integer in a double: the factored W-CRT's
-// digitize reads it for every limb (gemm.hip FoldSrc, qsrc 3), so the L-limb residue array never reaches HBM.
+// digitize reads it for every limb (wcrt_digitize.hpp FoldSrc, qsrc 3), so the L-limb residue array never reaches HBM.
 __global__ void gaussian_compact_kernel(double* e, int log_n, uint64_t total) {
     const uint64_t idx = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -125,7 +126,7 @@ __global__ void gaussian_compact_kernel(double* e, int log_n, uint64_t total) {
 }
 
 // The same draw once more, written as the one signed digit of e in the dense W-CRT GEMM's B layout (k-panel-major
-// [512 / 32][P][32] bytes, k = w, p = pos; gemm.hip mod_gemm_mfma_smallb_kernel), shared by every limb: |e| <= 27
+// [512 / 32][P][32] bytes, k = w, p = pos; wcrt_mfma.hpp mod_gemm_mfma_smallb_kernel), shared by every limb: |e| <= 27
 // (u1 >= 2^-53), so the int8 holds e exactly.  One thread per 4 consecutive k of one position (a 4-byte store), the
 // 8 threads of a position's 32-k panel row adjacent: every wave writes 2 KiB contiguous.
 __global__ void gaussian_i8_kernel(int8_t* __restrict__ b8, int log_n, uint32_t P) {
@@ -523,7 +524,7 @@ struct Bump {
 enum class WOut { Poly, Matrix, Vector };
 #define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
-// i8 MFMA operands for A = V or V^-1 (gemm.hip); leaves a on the VALU kernel when unavailable.  slot 1: the side
+// i8 MFMA operands for A = V or V^-1 (wcrt_gemm.hpp); leaves a on the VALU kernel when unavailable.  slot 1: the side
 // stream's digit planes (HeFork)
 static int use_mfma(mfhe_ctx* c, ModGemmArgs& a, const uint64_t* A, int L, int slot = 0) {
     if (!c->wcrt_mfma || !c->wD || (A != c->d_wV && A != c->d_wVinv)) return MFHE_OK;
@@ -547,7 +548,7 @@ static int use_mfma(mfhe_ctx* c, ModGemmArgs& a, const uint64_t* A, int L, int s
     a.epi = c->d_wepi;
     a.lds_stage = c->wcrt_mfma != 2;
     a.pipe = c->wcrt_pipe;
-    // mode 1: the forward transform of a per-limb V runs factored (half the MACs, gemm.hip)
+    // mode 1: the forward transform of a per-limb V runs factored (half the MACs, wcrt_digitize.hpp)
     if (c->wcrt_mfma == 1 && A == c->d_wV && a.aL && c->d_wZdig && a.epi) {
         a.Adig = c->d_wZdig;
         a.adL = (uint64_t)c->wD * 256 * 256;
@@ -565,12 +566,12 @@ static int use_mfma(mfhe_ctx* c, ModGemmArgs& a, const uint64_t* A, int L, int s
 }
 
 // qf (encode): B replaced by the W-IDFT's doubles, quantized and reduced inside the factored forward's digitize
-// kernel (gemm.hip mfma_digitize_fold_kernel<D, SRC>, and the encrypt samplers with it); only when quant_fused_ok(c)
+// kernel (wcrt_digitize.hpp mfma_digitize_fold_kernel<D, SRC>, and the encrypt samplers with it); only when quant_fused_ok(c)
 static bool quant_fused_ok(const mfhe_ctx* c) {
     return c->wcrt_mfma == 1 && c->wD && c->d_wZdig && c->d_wepi && c->d_wfold;
 }
 // the GEMM arguments of one W-CRT transform (wcrt_gemm launches them; encode / decode may launch two of them as
-// pairs, gemm.hip launch_mod_gemm_pair)
+// pairs, wcrt_gemm.hip launch_mod_gemm_pair)
 static int wcrt_args(mfhe_ctx* c, ModGemmArgs& a, const uint64_t* A, const uint64_t* B, bool b_poly, uint64_t* C,
                      WOut out, bool vector, int qsrc = 0, const double* qf = nullptr, uint64_t qf_step = 1,
                      const RingArgs* dec = nullptr, int slot = 0, uint64_t* C2 = nullptr) {
@@ -599,7 +600,7 @@ static int wcrt_args(mfhe_ctx* c, ModGemmArgs& a, const uint64_t* A, const uint6
     RC(use_mfma(c, a, A, g.L, slot));
     if (C2 && !a.fold) return set_error(MFHE_EINVAL, "W-CRT: a second output needs the factored forward");
     if (dec) {
-        // B is the ciphertext: the factored inverse's digitize decrypts it row by row (gemm.hip
+        // B is the ciphertext: the factored inverse's digitize decrypts it row by row (wcrt_digitize.hpp
         // mfma_digitize_ifold_dec_kernel); only where dec_fused_ok(c)
         if (!a.ifold) return set_error(MFHE_EINVAL, "W-CRT: a decrypt-fused source needs the factored inverse");
         a.dct = B;
@@ -631,7 +632,7 @@ static int wcrt_gemm(mfhe_ctx* c, const uint64_t* A, const uint64_t* B, bool b_p
 }
 
 // complex W-DFT / W-IDFT over [phi][n2]; MFHE_OPT_CGEMM_MFMA = 2 (default): factored through 771 = 3 x 257
-// (gemm.hip cgemm_mfma_kernel<1 / 2>), half the flops of the dense 512 x 512 product
+// (cdft.hip cgemm_mfma_kernel<1 / 2>), half the flops of the dense 512 x 512 product
 // planar (factored W-IDFT only, wdft_planar_ok): out as two [phi][n2] double planes, real then imaginary
 static bool wdft_planar_ok(const mfhe_ctx* c) { return c->cgemm_mfma >= 2 && c->d_wdZ; }
 static int wdft(mfhe_ctx* c, const double2* A, const double2* in, double2* out, hipStream_t s, bool planar = false) {
@@ -649,14 +650,14 @@ static int wdft(mfhe_ctx* c, const double2* A, const double2* in, double2* out, 
         f.P = 2 * f.Pf;
         f.scM = g.n2;
         if (A == c->d_wdV) {
-            // mode 2: the 257-point DFTs by Rader's algorithm (gemm.hip wdft_rader_kernel, r06); 3: the GEMM
+            // mode 2: the 257-point DFTs by Rader's algorithm (cdft.hip wdft_rader_kernel, r06); 3: the GEMM
             if (c->cgemm_mfma == 2 && c->d_wdrad && in != out)
                 return launch_wdft_rader(in, out, (uint32_t)g.n2, c->d_wdrad, c->d_wdgp, s);
             f.fac = 1;
             f.A = c->d_wdZ;
             return launch_cgemm(f, 1, s);
         }
-        if (c->cgemm_mfma == 2 && c->d_wdrad && in != out)   // Rader (gemm.hip wdft_rader_inv_kernel, r06)
+        if (c->cgemm_mfma == 2 && c->d_wdrad && in != out)   // Rader (cdft.hip wdft_rader_inv_kernel, r06)
             return launch_wdft_rader_inv(in, out, planar ? (double*)out + 512ull * g.n2 : nullptr, (uint32_t)g.n2,
                                          c->d_wdrad + 256, c->d_wdgp, c->d_wdlam, c->d_wdphi, s);
         const size_t need = (size_t)g.n2 * 2 * sizeof(double2);
@@ -691,8 +692,8 @@ static int wdft(mfhe_ctx* c, const double2* A, const double2* in, double2* out, 
 static int xy3(const mfhe_ctx* c, const double2* A, const double2* in, const double2* B, double2* tmp, double2* out,
                size_t lanes, hipStream_t s) {
     const Geo2 g = geo(c);
-    // n = 64: mode 2 by 64-point FFTs (gemm.hip xy_fft_kernel, equal to rounding); mode 3 both GEMMs in one launch
-    // (gemm.hip xy_fused_kernel), the same doubles as the two launches of mode 1
+    // n = 64: mode 2 by 64-point FFTs (cdft.hip xy_fft_kernel, equal to rounding); mode 3 both GEMMs in one launch
+    // (cdft.hip xy_fused_kernel), the same doubles as the two launches of mode 1
     if (c->cgemm_mfma == 2 && g.n == 64) {
         if (A == c->d_encV && B == c->d_encVT) return launch_xy_fft(in, out, false, (int)lanes, s);
         if (A == c->d_encVi && B == c->d_encViT) return launch_xy_fft(in, out, true, (int)lanes, s);
@@ -779,7 +780,7 @@ static int encode_impl(mfhe_ctx* c, const double* msg, uint64_t* out_re, uint64_
         const double* qre = (const double*)tmp;
         const double* qim = planar ? qre + 512ull * g.n2 : qre + 1;
         const uint64_t qstep = planar ? 1 : 2;
-        if (c->he_streams >= 2) {   // modes 2, 3: re and im as one launch per step (gemm.hip launch_mod_gemm_pair)
+        if (c->he_streams >= 2) {   // modes 2, 3: re and im as one launch per step (wcrt_gemm.hip launch_mod_gemm_pair)
             ModGemmArgs ar, ai;
             RC(wcrt_args(c, ar, c->d_wV, (const uint64_t*)tmp, false, out_re, WOut::Matrix, false, 1, qre, qstep));
             RC(wcrt_args(c, ai, c->d_wV, (const uint64_t*)tmp, false, out_im, WOut::Matrix, false, 1, qim, qstep,
@@ -818,7 +819,7 @@ static int decode_impl(mfhe_ctx* c, const uint64_t* ev_re, const uint64_t* ev_im
     // W-INTT (poly-major in -> matrix-major coeff), CRT compose + centre + /delta fused, into re / im (im on the side
     // stream with its own coefficient buffer; the two composes write alternate doubles of ccx)
     if (c->he_streams == 2) {
-        // re and im as one launch per step: W-INTT pair (gemm.hip launch_mod_gemm_pair), then one compose launch
+        // re and im as one launch per step: W-INTT pair (wcrt_gemm.hip launch_mod_gemm_pair), then one compose launch
         uint64_t* coeff_im = pb->get<uint64_t>(g.words);
         ModGemmArgs ar, ai;
         RC(wcrt_args(c, ar, c->d_wVinv, ev_re, true, coeff, WOut::Matrix, false, 0, nullptr, 1, dec));
@@ -878,14 +879,14 @@ static int encrypt_impl(mfhe_ctx* c, const uint64_t* m_re, const uint64_t* m_im,
     if (quant_fused_ok(c)) {
         // the samplers evaluated inside the factored W-CRT's digitize: a in place, e from one draw per coefficient;
         // with the fused ring, a straight into both ciphertexts' a halves (matrix-major), where enc_ring reads it.
-        // MFHE_OPT_HE_STREAMS 2: the two GEMMs as one launch (gemm.hip launch_mod_gemm_pair; measured no faster than
+        // MFHE_OPT_HE_STREAMS 2: the two GEMMs as one launch (wcrt_gemm.hip launch_mod_gemm_pair; measured no faster than
         // two: 301 vs 160 + 138 us, profiles/r05_he_stream_modes.txt, so mode 3 keeps two)
         const bool pair = c->he_streams == 2;
         ModGemmArgs aa, ae;
         if (a_mm) RC(wcrt_args(c, aa, c->d_wV, ap, false, ct_re + W, WOut::Matrix, false, 2, nullptr, 1, nullptr, 0,
                                m_im ? ct_im + W : nullptr));
         else RC(wcrt_args(c, aa, c->d_wV, ap, false, aev, WOut::Poly, false, 2));
-        // the noise: its W-CRT forward as the dense product with its one signed digit (MFHE_OPT_ENC_E_SMALL, gemm.hip
+        // the noise: its W-CRT forward as the dense product with its one signed digit (MFHE_OPT_ENC_E_SMALL, wcrt_mfma.hpp
         // mod_gemm_mfma_smallb_kernel) where the dense V planes have 5-6 digits; else factored from its residues
         const bool e_small = c->enc_e_small && !pair && c->d_wVdig && c->wD >= 5 && c->wD <= 6 && g.n2 % 64 == 0;
         if (e_small) {

@@ -103,9 +103,9 @@ struct mfhe_ctx {
     uint64_t* d_wrtab = nullptr; // [L][2 wD - 1][2] (256^s mod q, Shoup)
     int wD = 0;                  // 0: no MFMA tables (some q <= 2^27); else the plane stride (max digits)
     std::vector<int> wDl;        // digits limb l needs (<= wD): its higher planes are all zero
-    double* d_wepi = nullptr;    // [L][8] FP64 epilogue constants (gemm.hip GemmEpiF), null: integer epilogue
+    double* d_wepi = nullptr;    // [L][8] FP64 epilogue constants (wcrt_mfma.hpp mfma_epilogue), null: integer epilogue
     int8_t* d_wZdig = nullptr;   // [L][wD][256][256] digits of Z[i][k] = zeta^((i+1)(k+1)) (factored forward W-CRT)
-    double* d_wfold = nullptr;   // [L][16] factored forward fold constants (gemm.hip mfma_digitize_fold_kernel)
+    double* d_wfold = nullptr;   // [L][16] factored forward fold constants (wcrt_digitize.hpp mfma_digitize_fold_kernel)
     int8_t* d_wZidig = nullptr;  // [L][wD][256][256] digits of zeta^-((i+1)(k+1)) (factored inverse W-CRT)
     double* d_wifold = nullptr;  // [L][16] factored inverse constants (q, 1/q, lam1[2][3], lam2[2][3])
     double* d_wiz = nullptr;     // [L][48] x1, x2 (zeta^-255, zeta^-256), pad, x1^(16j+1), x2^(16j+1) for j < 16
@@ -162,13 +162,13 @@ struct mfhe_ctx {
     uint64_t* d_wVinv = nullptr;   // [L][512][512]  V_l^-1[r][w] (row-major)
     double2* d_wdV = nullptr;      // [512][512]     complex W-DFT
     double2* d_wdVinv = nullptr;   // [512][512]     its inverse (complex Gauss-Jordan)
-    // factored W-DFT (MFHE_OPT_CGEMM_MFMA = 2, gemm.hip): zeta = e^(2 pi i / 257)
+    // factored W-DFT (MFHE_OPT_CGEMM_MFMA = 2, cdft.hip): zeta = e^(2 pi i / 257)
     double2* d_wdZ = nullptr;      // [256][256] zeta^((i+1)(k+1))
     double2* d_wdZi = nullptr;     // [256][256] zeta^-((i+1)(k+1))
     double2* d_wdlam = nullptr;    // [2][2][3]  lam1 / lam2 [a'][t] of the inverse (771^-1 omega^-at differences)
     double2* d_wdxp = nullptr;     // [2][256]   zeta^(-255 b), zeta^(-256 b), b = 1..256
     int8_t* d_wdphi = nullptr;     // [513]      Phi_771 coefficients
-    // the forward factored W-DFT's 257-point DFTs by Rader's algorithm (gemm.hip wdft_rader_kernel, r06), g = 3:
+    // the forward factored W-DFT's 257-point DFTs by Rader's algorithm (cdft.hip wdft_rader_kernel, r06), g = 3:
     double2* d_wdrad = nullptr;    // [2][256]   FFT_256(zeta^(+-g^-k mod 257)) / 256: forward, inverse
     int16_t* d_wdgp = nullptr;     // [2][256]   g^n mod 257, g^-m mod 257
     void* wd_ws = nullptr;         // factored inverse W-DFT (c0, c1) per column, grown on demand

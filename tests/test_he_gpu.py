@@ -125,12 +125,12 @@ def test_wdft_and_xy_transforms_vs_oracle(mfhe, orc, small, cgemm):
 
 @pytest.mark.parametrize("n", [4, 16, 64])
 def test_cgemm_mfma_matches_valu(mfhe, n):
-    """f64 MFMA complex GEMM (gemm.hip cgemm_mfma_kernel) vs the VALU kernel at tile-ragged and full sizes:
+    """f64 MFMA complex GEMM (cdft.hip cgemm_mfma_kernel) vs the VALU kernel at tile-ragged and full sizes:
     XY-IDFT / XY-DFT (M = K = P = n per lane) and W-DFT / W-IDFT (M = K = 512, P = n^2), 1e-12 relative; the
     factored W-DFT (mode 2, default) too: its 256 x 256 zeta tables are single cos / sin values while the dense V
     (HE.cu:282-290) is a chain of products, so the two agree to rounding, not bit for bit.  At n = 64 mode 2 runs
-    XY by 64-point FFTs (gemm.hip xy_fft_kernel, r06), equal to rounding; mode 3 runs both XY products of a lane
-    in one launch (gemm.hip xy_fused_kernel): the same doubles as the two launches of mode 1, bit for bit."""
+    XY by 64-point FFTs (cdft.hip xy_fft_kernel, r06), equal to rounding; mode 3 runs both XY products of a lane
+    in one launch (cdft.hip xy_fused_kernel): the same doubles as the two launches of mode 1, bit for bit."""
     import torch
     ctx = mfhe.Context(RNS[:2], n.bit_length() - 1, CONV)
     assert ctx.get_option(mfhe.OPT_CGEMM_MFMA) == 2
@@ -162,7 +162,7 @@ def test_cgemm_mfma_matches_valu(mfhe, n):
         else:
             np.testing.assert_array_equal(outs[2][i], outs[3][i])
         np.testing.assert_array_equal(outs[3][i], outs[1][i])   # one launch (3) == two launches (1)
-    # mode 2 takes the factored W-DFT's 257-point DFTs by Rader's algorithm (gemm.hip wdft_rader_kernel and
+    # mode 2 takes the factored W-DFT's 257-point DFTs by Rader's algorithm (cdft.hip wdft_rader_kernel and
     # wdft_rader_inv_kernel, r06), mode 3 by the GEMM: equal to rounding
     for i in range(2, 4):
         assert np.max(np.abs(outs[2][i] - outs[3][i])) <= 1e-13 * np.max(np.abs(outs[3][i])), i
@@ -353,7 +353,7 @@ def _encrypt_decrypt_vs_oracle(mfhe, orc, n, ctx, h, moduli):
 @pytest.mark.parametrize("n,L", [(8, 11), (16, 3), (64, 11), (64, 1), (8, 16), (64, 16)])
 def test_encrypt_noise_small_operand_gemm_matches_factored(mfhe, n, L):
     """MFHE_OPT_ENC_E_SMALL (r06): the encrypt's Gaussian noise enters its W-CRT forward as the dense product with its
-    one signed digit (|e| <= 27 from the Box-Muller bound) and is never written as residues.  1 (default): gemm.hip
+    one signed digit (|e| <= 27 from the Box-Muller bound) and is never written as residues.  1 (default): wcrt_mfma.hpp
     mod_gemm_mfma_smallb_kernel, 64 x 128 tiles where n^2 % 128 == 0, else 64 x 64; 0: the factored forward of its
     residues.  The ciphertexts are identical, for limbs of 5 and 6 digits (the reference moduli: limb 0 has 44
     bits), one limb, and BASELINE C4's 16 x 35-bit primes; with a through both ciphertexts (ENC_A_DIRECT 1) or through
@@ -401,7 +401,7 @@ def test_encrypt_noise_small_operand_gemm_matches_factored(mfhe, n, L):
 def test_fused_ring_matches_unfused(mfhe, n, L):
     """encrypt_pair / decrypt_to_eval with the fused X-NTT * s * X-INTT row kernels (he.hip enc_ring_kernel,
     dec_ring_kernel; MFHE_OPT_HE_FUSED = 1, default) == the separate NTT / pointwise / combine kernels, bit-exact.
-    decrypt_and_decode too: at n = 64 the fused path decrypts inside the inverse W-CRT's digitize (gemm.hip
+    decrypt_and_decode too: at n = 64 the fused path decrypts inside the inverse W-CRT's digitize (wcrt_digitize.hpp
     mfma_digitize_ifold_dec_kernel), the unfused one through decrypt_to_eval and the plain digitize.  r05: the fused
     encrypt with the shared a written into both ciphertexts by the W-CRT GEMM (MFHE_OPT_ENC_A_DIRECT 1, default) and
     decode's re / im chains on two streams (MFHE_OPT_HE_STREAMS 1, default) against both off."""
@@ -519,7 +519,7 @@ def test_encode_stages_and_decode_vs_oracle(mfhe, orc, small):
     ref = h.decode(pre, pim)
     torch.cuda.synchronize()
     got = dout.cpu().numpy().view(np.complex128)
-    # FP64 stages: relative to the values (|msg| ~ 5e6 here).  The default W-DFT is factored (gemm.hip) with
+    # FP64 stages: relative to the values (|msg| ~ 5e6 here).  The default W-DFT is factored (cdft.hip) with
     # tables from single cos / sin values, the oracle's is the reference's dense chain-of-products V
     # (HE.cu:282-290): they agree to a few 1e-13 relative, not to 1e-6 absolute on 5e6 (the dense MFMA: 2e-13)
     assert np.max(np.abs(got - ref)) < 1e-12 * np.max(np.abs(ref))
@@ -542,7 +542,7 @@ def _ref_geometry_msg(pattern):
 def test_he_streams_encode_decode_identical(mfhe):
     """MFHE_OPT_HE_STREAMS: encode's re / im W-CRT chains and decode's W-INTT + compose chains on two streams
     (1: side chain with its own digit planes and coefficient buffer) or as one launch per step with grids over both
-    components (2: gemm.hip launch_mod_gemm_pair, the pair kernels) give the same words / doubles as one plain stream
+    components (2: wcrt_gemm.hip launch_mod_gemm_pair, the pair kernels) give the same words / doubles as one plain stream
     (0), at the reference geometry, called back to back."""
     import torch
     ctx = mfhe.Context(RNS, 6, CONV)
@@ -708,7 +708,7 @@ def test_kat7_kat8_encrypt_decrypt_reference_geometry(mfhe, pattern, tol):
 
 @pytest.mark.parametrize("n,L", [(8, 11), (64, 11), (4, 2), (16, 1)])
 def test_wcrt_mfma_matches_valu_and_oracle(mfhe, orc, n, L):
-    """W-CRT GEMM on i8 MFMA (digit-split exact product, gemm.hip) == the u128 VALU kernel == oracle,
+    """W-CRT GEMM on i8 MFMA (digit-split exact product, wcrt_gemm.hip) == the u128 VALU kernel == oracle,
     all three layouts (matrix->poly, poly->matrix, vector), bit-exact.  Modes: 1 = LDS-staged with the
     forward factored through 771 = 3 x 257 (default), 3 = LDS-staged dense, 2 = global fragments, 0 = VALU; the
     LDS-staged modes under each K pipeline (MFHE_OPT_WCRT_PIPE 0: auto, 1: two 64-k stages, 2: 4-slot 32-k ring,

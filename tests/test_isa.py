@@ -107,7 +107,7 @@ def test_column_pass_dma_waits_match_the_instruction_mix(inv, arith):
     r"_ZN4mfhe30mfma_digitize_ifold_dec_kernelILi6E[^>]*",
 ])
 def test_digitize_loads_are_not_serialised(kernel):
-    """The W-CRT digitize kernels (gemm.hip) must keep their column loads in flight together: a load under a
+    """The W-CRT digitize kernels (wcrt_digitize.hpp) must keep their column loads in flight together: a load under a
     `live ? x : 0` branch compiled to one branch per load, each followed by its own `s_waitcnt vmcnt(0)`, and a
     thread's 32 loads ran one at a time (70 -> 45 us once fixed).  Pinned here: no global load
     is followed by a vmcnt(0) within the next four instructions.  (The uniform-sampler source, SRC 2, computes its
@@ -127,7 +127,7 @@ def test_digitize_loads_are_not_serialised(kernel):
 
 @pytest.mark.parametrize("D,mode", [(5, 1), (6, 1), (5, 2), (6, 2)])
 def test_wcrt_ring_gemm_counted_waits(D, mode):
-    """mod_gemm_mfma_ring_kernel<D, MODE, false> (gemm.hip), the default factored forward (MODE 1) and inverse
+    """mod_gemm_mfma_ring_kernel<D, MODE, false> (wcrt_mfma.hpp), the default factored forward (MODE 1) and inverse
     (MODE 2) W-CRT GEMM: its K loop waits for stage s with a counted `s_waitcnt vmcnt(D)` / `vmcnt(2D)` (D = 5, four
     ring slots) or `vmcnt(D)` (D = 6, three slots) that leaves the next stages' D DMA instructions each in flight
     (ADVICE r03).  Pinned: D DMAs per 32-k stage (K = 256: 8
@@ -154,7 +154,7 @@ def test_wcrt_ring_gemm_counted_waits(D, mode):
 
 @pytest.mark.parametrize("mode", [1, 2])
 def test_wcrt_ring56_gemm_counted_waits(mode):
-    """mod_gemm_mfma_ring56_kernel<MODE> (gemm.hip, r04): the factored launch's D = 5 and D = 6 limbs in one grid, the
+    """mod_gemm_mfma_ring56_kernel<MODE> (wcrt_mfma.hpp, r04): the factored launch's D = 5 and D = 6 limbs in one grid, the
     two ring bodies behind a workgroup-uniform branch.  Each body keeps its own counted waits (D = 5: vmcnt 0 / 5 / 10,
     D = 6: 0 / 6), so the kernel holds 8 x (5 + 6) DMAs, 16 barriers, no scratch, no store and at most one other
     vector load per body inside the K loops, and 2 workgroups per CU worth of registers (<= 256 VGPRs)."""

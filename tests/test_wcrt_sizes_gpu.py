@@ -2,7 +2,7 @@
 
 The reference's W-CRT (init_wntt_tables + the wntt_forward/inverse_matrix kernels, /root/reference/src/core/HE.cu:
 237-273, 716-781) uses an __int128 % per product. It takes any prime q = 1 mod 771. This build has three
-W-CRT paths (csrc/gemm.hip, csrc/ctx.cpp build_wcrt):
+W-CRT paths (csrc/wcrt_gemm.hip, csrc/ctx.cpp build_wcrt):
 * i8 MFMA digit-split GEMMs, D = ceil(bits / 8) balanced base-256 digits, for 2^27 < q < 2^59:
   * D = 5 or 6 (q below ~2^46.99): factored (771 = 3 x 257) or dense;
   * D = 7 (up to ~2^54.99) and D = 8 (up to 2^59): dense only;

@@ -54,7 +54,7 @@ c1q=h[513]; c0q=(h[512]-c1q*phi[511])%q
 f=[(h[r]-c0q*phi[r]-(c1q*phi[r-1] if r>0 else 0))%q for r in range(512)]
 chk=[sum(pow(eta,e*r,q)*f[r] for r in range(512))%q for e in exp]
 print("inverse: V f == y:", chk == y, " f == x:", f == x)
-# the factored inverse as gemm.hip computes it: E_a[r2] (r2 = 1..256) from the 256 x 256 GEMM with
+# the factored inverse as wcrt_gemm.hip computes it: E_a[r2] (r2 = 1..256) from the 256 x 256 GEMM with
 # Zi[i][k] = zeta^-((i+1)(k+1)); E_a[0], E_a[255], E_a[256] also by dot products in the digitize kernel;
 # h_r2 = sum_a lam1[a][r2 % 3] E_a[r2], h_(r2+257) = sum_a lam2[a][r2 % 3] E_a[r2]; f_j = h_j - c0 phi_j - c1 phi_(j-1)
 kap=[[inv771*pow(om,(-(ap+1)*t)%3,q)%q for t in range(3)] for ap in range(2)]
