@@ -161,5 +161,42 @@ int bitlen(const std::vector<uint64_t>& a) {
     return 0;
 }
 
+bool bconv_tables(const uint64_t* src, int ns, const uint64_t* dst, int nd, BconvTables& t) {
+    if (ns <= 0 || nd < 0) return false;
+    for (int i = 0; i < ns; ++i)
+        if (src[i] < 2) return false;
+    for (int j = 0; j < nd; ++j)
+        if (dst[j] < 2) return false;
+    t.inv.assign(ns, 0);
+    t.inv_shoup.assign(ns, 0);
+    t.sinv.assign(ns, 0.0);
+    t.c.assign((size_t)nd * ns, 0);
+    t.smod.assign(nd, 0);
+    t.pinv.assign(nd, 0);
+    t.pinv_shoup.assign(nd, 0);
+    for (int i = 0; i < ns; ++i) {
+        const uint64_t s = src[i];
+        uint64_t m = 1 % s;   // S/s_i mod s_i
+        for (int k = 0; k < ns; ++k)
+            if (k != i) m = mulmod(m, src[k] % s, s);
+        t.inv[i] = invmod(m, s);
+        t.inv_shoup[i] = shoup(t.inv[i], s);
+        t.sinv[i] = 1.0 / (double)s;
+    }
+    for (int j = 0; j < nd; ++j) {
+        const uint64_t d = dst[j];
+        for (int i = 0; i < ns; ++i) {
+            uint64_t m = 1 % d;
+            for (int k = 0; k < ns; ++k)
+                if (k != i) m = mulmod(m, src[k] % d, d);
+            t.c[(size_t)j * ns + i] = m;
+        }
+        t.smod[j] = mulmod(t.c[(size_t)j * ns], src[0] % d, d);
+        t.pinv[j] = invmod(t.smod[j], d);
+        t.pinv_shoup[j] = shoup(t.pinv[j], d);
+    }
+    return true;
+}
+
 }  // namespace hm
 }  // namespace mfhe

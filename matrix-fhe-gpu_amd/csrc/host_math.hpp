@@ -58,5 +58,17 @@ bool complex_inverse_gj(std::vector<double>& a_ri, int dim, std::vector<double>&
 void big_mul_u64(const uint64_t* a, uint64_t m, uint64_t* out, int W);
 int bitlen(const std::vector<uint64_t>& a);
 
+// RNS basis conversion tables (bconv.hip) for a source basis s_0 .. s_(ns-1) with product S and destination
+// moduli d_0 .. d_(nd-1), all pairwise distinct primes:
+//   inv[i]  = (S/s_i)^-1 mod s_i, inv_shoup[i] its Shoup companion      sinv[i] = 1/s_i as f64
+//   c[j*ns + i] = (S/s_i) mod d_j                                        smod[j] = S mod d_j
+//   pinv[j] = S^-1 mod d_j with pinv_shoup[j] (ModDown: the dropped limbs are the source, P = S)
+struct BconvTables {
+    std::vector<uint64_t> inv, inv_shoup, c, smod, pinv, pinv_shoup;
+    std::vector<double> sinv;
+};
+// false for an empty source or a modulus < 2
+bool bconv_tables(const uint64_t* src, int ns, const uint64_t* dst, int nd, BconvTables& t);
+
 }  // namespace hm
 }  // namespace mfhe

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -181,6 +182,15 @@ struct mfhe_ctx {
     // pipeline workspace (allocated on first use / mfhe_ctx_reserve_workspace)
     void* ws = nullptr;
     size_t ws_bytes = 0;
+
+    // RNS basis conversion tables (bconv.hip), built on first use or by mfhe_rns_bconv_reserve: one device table
+    // per (source range, destination range), owned by allocs
+    struct BconvEntry {
+        int src_start, src_count, dst_start, dst_count;
+        uint64_t* d_tab;
+    };
+    std::vector<BconvEntry> bconv;
+    std::mutex bconv_mu;
 
     std::vector<void*> allocs;  // everything above, freed at destroy
 };

@@ -27,6 +27,7 @@ OPT_NTT_CHUNK_BYTES, OPT_NTT_PLAN, OPT_CRT_WORDS, OPT_NTT_WG_PER_CU, OPT_NTT_PRE
 OPT_NTT_FUSED, OPT_WCRT_MFMA = 6, 9   # OPT_NTT_FUSED: removed in r04, only 0 accepted
 OPT_CGEMM_MFMA, OPT_HE_FUSED, OPT_TRACE_SPLIT = 10, 11, 12
 XCHG_ALLGATHER, XCHG_ALLTOALL = 0, 1
+BCONV_FAST, BCONV_CENTERED = 0, 1
 RECOMBINE_ROWS_GLOBAL = 1
 RECOMBINE_EXCHANGE_ONLY = 2     # measurement: exchanges only, composes skipped (out untouched)
 RECOMBINE_AFTER_PREV = 4        # the shard was complete when the previous chunked call on the comm was entered
@@ -111,6 +112,14 @@ _sig("mfhe_crt_to_f64", [_vp, _vp, _vp, _sz, _vp, _sz, _vp])
 _sig("mfhe_crt_compose_i64", [_vp, _vp, _sz, _sz, _vp, _vp])
 _sig("mfhe_crt_compose_f64", [_vp, _vp, _sz, _sz, _vp, _sz, _vp])
 _sig("mfhe_crt_compose_f64_sharded", [_vp, _vp, ctypes.c_int, _sz, _sz, _sz, _vp, _sz, _vp])
+_int = ctypes.c_int
+_sig("mfhe_rns_bconv_reserve", [_vp, _int, _int, _int, _int])
+_sig("mfhe_rns_bconv", [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_rns_moddown", [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _vp])
+_sig("mfhe_rns_modup", [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_ntt_bconv_reserve", [_vp, _sz, _int])
+_sig("mfhe_ntt_modup", [_vp, _vp, _sz, _vp, _sz, _sz, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_ntt_moddown", [_vp, _vp, _sz, _vp, _sz, _sz, _int, _int, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -400,6 +409,91 @@ class Context:
                                                ncoeff, _ptr(out), out_stride, _stream_ptr(stream)),
               "crt_compose_f64_sharded")
         return out
+
+    # ---- RNS basis conversion (include/mfhe.h): residues [npoly][rows][ncoeff], poly strides in words ----
+    @staticmethod
+    def _need_polys(t, npoly, stride, rows, ncoeff, what):
+        """npoly blocks of rows * ncoeff words, `stride` words apart."""
+        _need(t, (npoly - 1) * stride + rows * ncoeff if npoly and ncoeff else 0, what)
+
+    def rns_bconv_reserve(self, src_start, src_count, dst_start, dst_count):
+        check(lib.mfhe_rns_bconv_reserve(self._h, src_start, src_count, dst_start, dst_count), "rns_bconv_reserve")
+
+    def rns_bconv(self, src, dst, npoly, ncoeff, src_start, src_count, dst_start, dst_count, mode=BCONV_FAST,
+                  in_stride=None, out_stride=None, stream=None):
+        """dst rows = limbs [dst_start, +dst_count) converted from src rows = limbs [src_start, +src_count)."""
+        ist = src_count * ncoeff if in_stride is None else in_stride
+        ost = dst_count * ncoeff if out_stride is None else out_stride
+        self._need_polys(src, npoly, ist, src_count, ncoeff, "rns_bconv src")
+        self._need_polys(dst, npoly, ost, dst_count, ncoeff, "rns_bconv dst")
+        check(lib.mfhe_rns_bconv(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, ncoeff, src_start, src_count,
+                                 dst_start, dst_count, mode, _stream_ptr(stream)), "rns_bconv")
+        return dst
+
+    def rns_moddown_reserve(self, keep_count, drop_start, drop_count):
+        self.rns_bconv_reserve(drop_start, drop_count, 0, keep_count)
+
+    def rns_moddown(self, src, dst, npoly, ncoeff, keep_count, drop_start, drop_count, in_stride=None,
+                    out_stride=None, stream=None):
+        """src rows: limbs [0, keep_count) then [drop_start, +drop_count); dst rows [0, keep_count) =
+        round(x / prod(dropped)).  dst may be src (in place, equal strides)."""
+        ist = (keep_count + drop_count) * ncoeff if in_stride is None else in_stride
+        ost = (ist if dst is src else keep_count * ncoeff) if out_stride is None else out_stride
+        self._need_polys(src, npoly, ist, keep_count + drop_count, ncoeff, "rns_moddown src")
+        self._need_polys(dst, npoly, ost, keep_count, ncoeff, "rns_moddown dst")
+        check(lib.mfhe_rns_moddown(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, ncoeff, keep_count, drop_start,
+                                   drop_count, _stream_ptr(stream)), "rns_moddown")
+        return dst
+
+    def rns_rescale(self, src, dst, npoly, ncoeff, level, in_stride=None, out_stride=None, stream=None):
+        """Drop limb level - 1 of a level-limb polynomial: dst rows [0, level - 1) = round(x / q_(level-1))."""
+        return self.rns_moddown(src, dst, npoly, ncoeff, level - 1, level - 1, 1, in_stride, out_stride, stream)
+
+    def _modup_ranges(self, level, digit_start, digit_count, special_start, nspecial):
+        rs = [(0, digit_start), (digit_start + digit_count, level - digit_start - digit_count),
+              (special_start, nspecial)]
+        return [(a, n) for a, n in rs if n > 0]
+
+    def rns_modup_reserve(self, level, digit_start, digit_count, special_start, nspecial):
+        for a, n in self._modup_ranges(level, digit_start, digit_count, special_start, nspecial):
+            self.rns_bconv_reserve(digit_start, digit_count, a, n)
+
+    def rns_modup(self, src, dst, npoly, ncoeff, level, digit_start, digit_count, special_start, nspecial,
+                  in_stride=None, out_stride=None, stream=None):
+        """src rows: limbs [0, level); dst rows: [0, level) then [special_start, +nspecial): the digit's rows
+        copied, every other row its FAST conversion.  One launch."""
+        ist = level * ncoeff if in_stride is None else in_stride
+        ost = (level + nspecial) * ncoeff if out_stride is None else out_stride
+        self._need_polys(src, npoly, ist, level, ncoeff, "rns_modup src")
+        self._need_polys(dst, npoly, ost, level + nspecial, ncoeff, "rns_modup dst")
+        check(lib.mfhe_rns_modup(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, ncoeff, level, digit_start,
+                                 digit_count, special_start, nspecial, _stream_ptr(stream)), "rns_modup")
+        return dst
+
+    def ntt_bconv_reserve(self, npoly, rows):
+        check(lib.mfhe_ntt_bconv_reserve(self._h, npoly, rows), "ntt_bconv_reserve")
+
+    def ntt_modup(self, src, dst, npoly, level, digit_start, digit_count, special_start, nspecial, in_stride=None,
+                  out_stride=None, stream=None):
+        """rns_modup on evaluation-domain rows (phantom NTT, ncoeff = N)."""
+        ist = level * self.N if in_stride is None else in_stride
+        ost = (level + nspecial) * self.N if out_stride is None else out_stride
+        self._need_polys(src, npoly, ist, level, self.N, "ntt_modup src")
+        self._need_polys(dst, npoly, ost, level + nspecial, self.N, "ntt_modup dst")
+        check(lib.mfhe_ntt_modup(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, level, digit_start, digit_count,
+                                 special_start, nspecial, _stream_ptr(stream)), "ntt_modup")
+        return dst
+
+    def ntt_moddown(self, src, dst, npoly, keep_count, drop_start, drop_count, in_stride=None, out_stride=None,
+                    stream=None):
+        """rns_moddown on evaluation-domain rows (phantom NTT, ncoeff = N)."""
+        ist = (keep_count + drop_count) * self.N if in_stride is None else in_stride
+        ost = (ist if dst is src else keep_count * self.N) if out_stride is None else out_stride
+        self._need_polys(src, npoly, ist, keep_count + drop_count, self.N, "ntt_moddown src")
+        self._need_polys(dst, npoly, ost, keep_count, self.N, "ntt_moddown dst")
+        check(lib.mfhe_ntt_moddown(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, keep_count, drop_start,
+                                   drop_count, _stream_ptr(stream)), "ntt_moddown")
+        return dst
 
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
         """RCCL exchange of this rank's [npoly][L/G][ncoeff] residue shard + compose of its polynomial slice
