@@ -18,49 +18,13 @@
 #include <cstring>
 
 #include "host_math.hpp"
+#include "mod128.hpp"
 
 namespace mfhe {
-
-using u128 = unsigned __int128;
 
 // largest template-unrolled source count: 16 y values (32 VGPRs) at two coefficients, every instantiation at
 // <= 63 VGPRs and 8 waves/SIMD (compiler resource usage)
 constexpr int kBconvUnroll = 8;
-
-__device__ __forceinline__ uint64_t shoup_mul(uint64_t x, uint64_t w, uint64_t ws, uint64_t q) {
-    const uint64_t r = x * w - __umul64hi(x, ws) * q;   // [0, 2q)
-    return r >= q ? r - q : r;
-}
-
-// x mod q for any 128-bit x, (r0, r1) = floor(2^128 / q): the quotient estimate floor(x (r0, r1) / 2^128) is exact or
-// one low, so one conditional subtraction canonicalises
-__device__ __forceinline__ uint64_t barrett128(u128 x, uint64_t q, uint64_t r0, uint64_t r1) {
-    const uint64_t x0 = (uint64_t)x, x1 = (uint64_t)(x >> 64);
-    const u128 a = (u128)x0 * r1 + __umul64hi(x0, r0);
-    const u128 b = (u128)x1 * r0 + (uint64_t)a;
-    const uint64_t qhat = x1 * r1 + (uint64_t)(a >> 64) + (uint64_t)(b >> 64);
-    const uint64_t r = x0 - qhat * q;
-    return r >= q ? r - q : r;
-}
-
-template <int V>
-struct Lane;
-template <>
-struct Lane<1> {
-    using T = uint64_t;
-    static __device__ __forceinline__ void load(const T* p, uint64_t (&x)[1]) { x[0] = *p; }
-    static __device__ __forceinline__ void store(T* p, const uint64_t (&x)[1]) { *p = x[0]; }
-};
-template <>
-struct Lane<2> {
-    using T = ulonglong2;
-    static __device__ __forceinline__ void load(const T* p, uint64_t (&x)[2]) {
-        const T v = *p;
-        x[0] = v.x;
-        x[1] = v.y;
-    }
-    static __device__ __forceinline__ void store(T* p, const uint64_t (&x)[2]) { *p = make_ulonglong2(x[0], x[1]); }
-};
 
 __device__ __forceinline__ double bits_to_f64(uint64_t b) { return __longlong_as_double((long long)b); }
 
@@ -199,10 +163,12 @@ __global__ __launch_bounds__(256) void bconv_copy_rows_kernel(const uint64_t* __
 }
 
 // ModDown tail in the evaluation domain: out[p][j][c] = (in[p][j][c] - r[p][j][c]) P^-1 mod q_j, j < keep;
-// r dense [npoly][keep][N].  out may equal in.
+// r [npoly][keep][N], r_stride words per polynomial.  out may equal in.  add (may be null, may equal out): the same
+// layout as out, added to the result mod q_j (the key switch's MFHE_KS_ADD).
 __global__ __launch_bounds__(256) void bconv_sub_scale_kernel(const uint64_t* in, uint64_t in_stride,
-                                                              const uint64_t* __restrict__ r, uint64_t* out,
-                                                              uint64_t out_stride, int keep, int logN, int ns,
+                                                              const uint64_t* __restrict__ r, uint64_t r_stride,
+                                                              uint64_t* out, uint64_t out_stride, const uint64_t* add,
+                                                              int keep, int logN, int ns,
                                                               const uint64_t* __restrict__ tab,
                                                               const uint64_t* __restrict__ dmod, uint64_t total) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -212,9 +178,14 @@ __global__ __launch_bounds__(256) void bconv_sub_scale_kernel(const uint64_t* in
     const uint64_t* h = tab + (uint64_t)kBconvSrcWords * ns + j * (uint64_t)(kBconvDstHead + ns);
     const uint64_t q = dmod[3 * j];
     const uint64_t off = (j << logN) + c;
-    const uint64_t x = in[p * in_stride + off], rr = r[i];
+    const uint64_t x = in[p * in_stride + off], rr = r[p * r_stride + off];
     const uint64_t t = x >= rr ? x - rr : x + q - rr;
-    out[p * out_stride + off] = shoup_mul(t, h[1], h[2], q);
+    uint64_t v = shoup_mul(t, h[1], h[2], q);
+    if (add) {
+        v += add[p * out_stride + off];
+        v = v >= q ? v - q : v;
+    }
+    out[p * out_stride + off] = v;
 }
 
 int bconv_table(mfhe_ctx* c, int ss, int sc, int ds, int dc, const uint64_t** tab) {
@@ -330,11 +301,7 @@ static int check_buffers(const void* in, size_t in_stride, size_t in_rows, const
     return MFHE_OK;
 }
 
-struct ModUpPlan {
-    int nr = 0;
-    int limb[3], row[3], count[3];
-};
-static int check_modup(const mfhe_ctx* c, int level, int ds, int dc, int sp, int nsp, ModUpPlan& pl) {
+int check_modup(const mfhe_ctx* c, int level, int ds, int dc, int sp, int nsp, ModUpPlan& pl) {
     if (level < 1 || level > c->L) return set_error(MFHE_EINVAL, "modup: level outside the context");
     if (ds < 0 || dc < 1 || ds > level || dc > level - ds) return set_error(MFHE_EINVAL, "modup: digit outside [0, level)");
     if (nsp < 0 || sp < 0 || sp > c->L || nsp > c->L - sp) return set_error(MFHE_EINVAL, "modup: special limbs outside the context");
@@ -357,13 +324,96 @@ static int check_moddown(const mfhe_ctx* c, int keep, int drop_start, int drop_c
     return check_range(c, drop_start, drop_count, "moddown");
 }
 
-static int grow_ws(mfhe_ctx* c, size_t need) {
+int grow_ws(mfhe_ctx* c, size_t need) {
     if (c->ws_bytes >= need) return MFHE_OK;
     if (c->ws) MFHE_HIP(hipFree(c->ws));
     c->ws = nullptr;
     c->ws_bytes = 0;
     MFHE_HIP(hipMalloc(&c->ws, need));
     c->ws_bytes = need;
+    return MFHE_OK;
+}
+
+// ---- NTT-domain bodies with the scratch base as an argument (the public calls pass the context workspace; the key
+// switch passes a part of its own block) ----
+int ntt_modup_tables(mfhe_ctx* c, int digit_start, int digit_count, const ModUpPlan& pl, const uint64_t* tab[3]) {
+    for (int k = 0; k < 3; ++k) tab[k] = nullptr;
+    for (int k = 0; k < pl.nr; ++k) {
+        int rc = bconv_table(c, digit_start, digit_count, pl.limb[k], pl.count[k], &tab[k]);
+        if (rc) return rc;
+    }
+    return MFHE_OK;
+}
+
+// scratch: npoly * (level + nspecial) * N words
+int ntt_modup_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* d_out, size_t out_stride,
+                   size_t npoly, int digit_start, int digit_count, const ModUpPlan& pl, const uint64_t* const tab[3],
+                   uint64_t* scratch, hipStream_t st) {
+    const size_t N = c->N;
+    mfhe_stream_t s = (mfhe_stream_t)st;
+    int rc;
+    // digit rows pass through
+    if (d_in != d_out || in_stride != out_stride)
+        if ((rc = launch_copy_rows(d_in + (size_t)digit_start * N, in_stride, d_out + (size_t)digit_start * N,
+                                   out_stride, npoly, (size_t)digit_count * N, st)))
+            return rc;
+    if (pl.nr == 0) return MFHE_OK;
+    uint64_t* dig = scratch;   // [npoly][digit_count][N]
+    if ((rc = launch_copy_rows(d_in + (size_t)digit_start * N, in_stride, dig, (size_t)digit_count * N, npoly,
+                               (size_t)digit_count * N, st)))
+        return rc;
+    if ((rc = mfhe_ntt_inv(c, dig, npoly, digit_start, digit_count, s))) return rc;
+    uint64_t* blk = dig + npoly * (size_t)digit_count * N;
+    for (int k = 0; k < pl.nr; ++k) {
+        const size_t bw = (size_t)pl.count[k] * N;   // [npoly][count][N]
+        BconvArgs a{};
+        a.in = dig; a.out = blk; a.in_stride = (size_t)digit_count * N; a.out_stride = bw; a.ncoeff = N;
+        a.ns = digit_count; a.src_row = 0; a.copy_row = -1; a.nr = 1;
+        a.r[0].tab = tab[k]; a.r[0].limb = pl.limb[k]; a.r[0].row = 0; a.r[0].count = pl.count[k];
+        a.dmod = c->d_dmod;
+        if ((rc = launch_bconv(a, npoly, kBconvFast, st))) return rc;
+        if ((rc = mfhe_ntt_fwd(c, blk, npoly, pl.limb[k], pl.count[k], s))) return rc;
+        if ((rc = launch_copy_rows(blk, bw, d_out + (size_t)pl.row[k] * N, out_stride, npoly, bw, st))) return rc;
+        blk += npoly * bw;
+    }
+    return MFHE_OK;
+}
+
+// The centred conversion of the dropped rows, forward-transformed: *cen = [npoly][keep_count][N] inside scratch
+// (npoly * (keep_count + drop_count) * N words).
+int ntt_moddown_center(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, size_t npoly, int keep_count,
+                       int drop_start, int drop_count, const uint64_t* tab, uint64_t* scratch, const uint64_t** cen_out,
+                       hipStream_t st) {
+    const size_t N = c->N;
+    mfhe_stream_t s = (mfhe_stream_t)st;
+    int rc;
+    uint64_t* drp = scratch;                                   // [npoly][drop_count][N]
+    uint64_t* cen = drp + npoly * (size_t)drop_count * N;     // [npoly][keep_count][N]
+    const size_t dw = (size_t)drop_count * N, kw = (size_t)keep_count * N;
+    if ((rc = launch_copy_rows(d_in + kw, in_stride, drp, dw, npoly, dw, st))) return rc;
+    if ((rc = mfhe_ntt_inv(c, drp, npoly, drop_start, drop_count, s))) return rc;
+    BconvArgs a{};
+    a.in = drp; a.out = cen; a.in_stride = dw; a.out_stride = kw; a.ncoeff = N;
+    a.ns = drop_count; a.src_row = 0; a.copy_row = -1; a.nr = 1;
+    a.r[0].tab = tab; a.r[0].limb = 0; a.r[0].row = 0; a.r[0].count = keep_count;
+    a.dmod = c->d_dmod;
+    if ((rc = launch_bconv(a, npoly, kBconvCentered, st))) return rc;
+    if ((rc = mfhe_ntt_fwd(c, cen, npoly, 0, keep_count, s))) return rc;
+    *cen_out = cen;
+    return MFHE_OK;
+}
+
+int launch_sub_scale(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const uint64_t* cen, size_t cen_stride,
+                     uint64_t* d_out, size_t out_stride, const uint64_t* d_add, size_t npoly, int keep_count,
+                     int drop_count, const uint64_t* tab, hipStream_t st) {
+    const uint64_t total = (uint64_t)npoly * keep_count * c->N;
+    const uint64_t blocks = (total + 255) / 256;
+    if (blocks == 0) return MFHE_OK;
+    if (blocks > 0x7fffffffull) return set_error(MFHE_EINVAL, "ntt_moddown: too many coefficients for one launch");
+    hipLaunchKernelGGL(bconv_sub_scale_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, d_in, (uint64_t)in_stride, cen,
+                       (uint64_t)cen_stride, d_out, (uint64_t)out_stride, d_add, keep_count, c->logN, drop_count, tab,
+                       (const uint64_t*)c->d_dmod, total);
+    MFHE_CHECK_LAUNCH("bconv_sub_scale_kernel");
     return MFHE_OK;
 }
 
@@ -466,33 +516,11 @@ extern "C" int mfhe_ntt_modup(mfhe_ctx* c, const uint64_t* d_in, size_t in_strid
     const size_t N = c->N;
     RC(check_buffers(d_in, in_stride, level, d_out, out_stride, (size_t)level + nspecial, N, "ntt_modup"));
     if (npoly == 0) return MFHE_OK;
-    hipStream_t st = (hipStream_t)s;
-    const uint64_t* tab[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < pl.nr; ++k) RC(bconv_table(c, digit_start, digit_count, pl.limb[k], pl.count[k], &tab[k]));
+    const uint64_t* tab[3];
+    RC(ntt_modup_tables(c, digit_start, digit_count, pl, tab));
     RC(grow_ws(c, npoly * ((size_t)level + nspecial) * N * 8));
-    // digit rows pass through
-    if (d_in != d_out || in_stride != out_stride)
-        RC(launch_copy_rows(d_in + (size_t)digit_start * N, in_stride, d_out + (size_t)digit_start * N, out_stride,
-                            npoly, (size_t)digit_count * N, st));
-    if (pl.nr == 0) return MFHE_OK;
-    uint64_t* dig = (uint64_t*)c->ws;   // [npoly][digit_count][N]
-    RC(launch_copy_rows(d_in + (size_t)digit_start * N, in_stride, dig, (size_t)digit_count * N, npoly,
-                        (size_t)digit_count * N, st));
-    RC(mfhe_ntt_inv(c, dig, npoly, digit_start, digit_count, s));
-    uint64_t* blk = dig + npoly * (size_t)digit_count * N;
-    for (int k = 0; k < pl.nr; ++k) {
-        const size_t bw = (size_t)pl.count[k] * N;   // [npoly][count][N]
-        BconvArgs a{};
-        a.in = dig; a.out = blk; a.in_stride = (size_t)digit_count * N; a.out_stride = bw; a.ncoeff = N;
-        a.ns = digit_count; a.src_row = 0; a.copy_row = -1; a.nr = 1;
-        a.r[0].tab = tab[k]; a.r[0].limb = pl.limb[k]; a.r[0].row = 0; a.r[0].count = pl.count[k];
-        a.dmod = c->d_dmod;
-        RC(launch_bconv(a, npoly, kBconvFast, st));
-        RC(mfhe_ntt_fwd(c, blk, npoly, pl.limb[k], pl.count[k], s));
-        RC(launch_copy_rows(blk, bw, d_out + (size_t)pl.row[k] * N, out_stride, npoly, bw, st));
-        blk += npoly * bw;
-    }
-    return MFHE_OK;
+    return ntt_modup_body(c, d_in, in_stride, d_out, out_stride, npoly, digit_start, digit_count, pl, tab,
+                          (uint64_t*)c->ws, (hipStream_t)s);
 }
 
 extern "C" int mfhe_ntt_moddown(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* d_out,
@@ -509,24 +537,8 @@ extern "C" int mfhe_ntt_moddown(mfhe_ctx* c, const uint64_t* d_in, size_t in_str
     const uint64_t* tab = nullptr;
     RC(bconv_table(c, drop_start, drop_count, 0, keep_count, &tab));
     RC(grow_ws(c, npoly * ((size_t)keep_count + drop_count) * N * 8));
-    uint64_t* drp = (uint64_t*)c->ws;                          // [npoly][drop_count][N]
-    uint64_t* cen = drp + npoly * (size_t)drop_count * N;     // [npoly][keep_count][N]
-    const size_t dw = (size_t)drop_count * N, kw = (size_t)keep_count * N;
-    RC(launch_copy_rows(d_in + kw, in_stride, drp, dw, npoly, dw, st));
-    RC(mfhe_ntt_inv(c, drp, npoly, drop_start, drop_count, s));
-    BconvArgs a{};
-    a.in = drp; a.out = cen; a.in_stride = dw; a.out_stride = kw; a.ncoeff = N;
-    a.ns = drop_count; a.src_row = 0; a.copy_row = -1; a.nr = 1;
-    a.r[0].tab = tab; a.r[0].limb = 0; a.r[0].row = 0; a.r[0].count = keep_count;
-    a.dmod = c->d_dmod;
-    RC(launch_bconv(a, npoly, kBconvCentered, st));
-    RC(mfhe_ntt_fwd(c, cen, npoly, 0, keep_count, s));
-    const uint64_t total = (uint64_t)npoly * kw;
-    const uint64_t blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffull) return set_error(MFHE_EINVAL, "ntt_moddown: too many coefficients for one launch");
-    hipLaunchKernelGGL(bconv_sub_scale_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, d_in, (uint64_t)in_stride,
-                       (const uint64_t*)cen, d_out, (uint64_t)out_stride, keep_count, c->logN, drop_count, tab,
-                       (const uint64_t*)c->d_dmod, total);
-    MFHE_CHECK_LAUNCH("bconv_sub_scale_kernel");
-    return MFHE_OK;
+    const uint64_t* cen = nullptr;
+    RC(ntt_moddown_center(c, d_in, in_stride, npoly, keep_count, drop_start, drop_count, tab, (uint64_t*)c->ws, &cen, st));
+    return launch_sub_scale(c, d_in, in_stride, cen, (size_t)keep_count * N, d_out, out_stride, nullptr, npoly,
+                            keep_count, drop_count, tab, st);
 }

@@ -40,4 +40,32 @@ int bconv_table(mfhe_ctx* c, int src_start, int src_count, int dst_start, int ds
 // ncoeff and both strides are even and both buffers 16-byte aligned).  kernel_mode: kBconv*.
 int launch_bconv(BconvArgs a, size_t npoly, int kernel_mode, hipStream_t st);
 
+// ---- shared with keyswitch.hip ----
+// Grow the context workspace to `need` bytes (frees and reallocates; nothing when it is large enough).
+int grow_ws(mfhe_ctx* c, size_t need);
+
+// The destination ranges of a ModUp of digit [ds, ds + dc) at `level`: below the digit, above it, the special limbs
+// (the non-empty ones), each with its first context limb, its first output row and its count.
+struct ModUpPlan {
+    int nr = 0;
+    int limb[3], row[3], count[3];
+};
+int check_modup(const mfhe_ctx* c, int level, int ds, int dc, int sp, int nsp, ModUpPlan& pl);
+int ntt_modup_tables(mfhe_ctx* c, int digit_start, int digit_count, const ModUpPlan& pl, const uint64_t* tab[3]);
+
+// Bodies of mfhe_ntt_modup / mfhe_ntt_moddown (arguments already checked, tables already built) with the scratch base
+// as an argument.  ntt_modup_body: scratch of npoly * (level + nspecial) * N words.  ntt_moddown_center: scratch of
+// npoly * (keep_count + drop_count) * N words; *cen = the centred conversion of the dropped rows in the evaluation
+// domain, dense [npoly][keep_count][N] inside scratch.  launch_sub_scale: ModDown's tail,
+// out = (in - cen) P^-1 (+ d_add, same layout as out, when not null) on the kept rows.
+int ntt_modup_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* d_out, size_t out_stride,
+                   size_t npoly, int digit_start, int digit_count, const ModUpPlan& pl, const uint64_t* const tab[3],
+                   uint64_t* scratch, hipStream_t st);
+int ntt_moddown_center(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, size_t npoly, int keep_count,
+                       int drop_start, int drop_count, const uint64_t* tab, uint64_t* scratch, const uint64_t** cen,
+                       hipStream_t st);
+int launch_sub_scale(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const uint64_t* cen, size_t cen_stride,
+                     uint64_t* d_out, size_t out_stride, const uint64_t* d_add, size_t npoly, int keep_count,
+                     int drop_count, const uint64_t* tab, hipStream_t st);
+
 }  // namespace mfhe

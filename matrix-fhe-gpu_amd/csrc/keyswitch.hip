@@ -1,0 +1,370 @@
+// keyswitch.hip -- hybrid key switching for gfx950: switching-key assembly, the digit-by-key inner product and the
+// driver that chains ModUp, inner product and ModDown (include/mfhe.h mfhe_ksk_assemble, mfhe_ksk_inner_product,
+// mfhe_keyswitch).
+//
+// Everything is in the evaluation domain (phantom NTT) and canonical.  Digits are runs of alpha consecutive Q limbs;
+// a call at `level` has beta = ceil(level / alpha) of them.  A (level + K)-row block has modulus limb r on row
+// r < level, else limb special_start + r - level; a key made at key_level keeps its special rows at key rows
+// key_level .. key_level + K - 1 and serves every level <= key_level.
+//
+//   assemble      : ksk[j][1] = a_j, ksk[j][0][r] = e_j - a_j s_to + F s_from mod q_r, F = P mod q_r when limb r lies
+//                   in digit j, else 0 (P = product of the special moduli)
+//   inner product : acc[p][c][r] = sum_j raised[j][p][r] ksk[j][c][keyrow(r)] mod q_r
+//   keyswitch     : raise every digit (ModUp), inner product, ModDown both components by the special limbs
+//
+// Inner product design: one thread owns one (row, coefficient) -- two adjacent coefficients with 16-byte loads and
+// stores when the layout allows -- and walks a run of polynomials with its slice of the key held in registers
+// (ndigits <= kKsipUnroll; longer keys are re-read per polynomial, from the cache).  Both components accumulate as
+// unreduced u128 sums (products of canonical residues of moduli < 2^62 are < 2^124, so 16 fit; longer sums reduce
+// every 16 terms) and end in one 128-bit Barrett reduction against d_dmod.  The row is the grid's y index, so the
+// modulus constants are wave-uniform scalar loads.
+#include "keyswitch.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include "bconv.hpp"
+#include "host_math.hpp"
+#include "mod128.hpp"
+
+namespace mfhe {
+
+// largest digit count whose key slice stays in registers: 2 * 6 * 2 u64 at two coefficients
+constexpr int kKsipUnroll = 6;
+// shortest run of polynomials one thread walks with its key slice (the whole batch when it is smaller)
+constexpr uint64_t kKsipMinRun = 4;
+
+// ND: digits (template-unrolled, the key slice in registers) or 0 (generic loop over a.ndigits); V: coefficients per
+// thread.  dmod is a __restrict__ kernel parameter, indexed by the block's row: scalar loads.
+template <int ND, int V>
+__global__ __launch_bounds__(256) void ksk_inner_product_kernel(KsipArgs a, const uint64_t* __restrict__ dmod) {
+    using T = typename Lane<V>::T;
+    const uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (c >= a.ncoeff) return;
+    const int r = blockIdx.y;
+    const int level = a.g.level, rows = level + a.g.nspecial;
+    const int limb = r < level ? r : a.g.special_start + r - level;
+    const int krow = r < level ? r : a.g.key_level + r - level;
+    const uint64_t q = dmod[3 * limb], r0 = dmod[3 * limb + 1], r1 = dmod[3 * limb + 2];
+    const uint64_t kcs = (uint64_t)(a.g.key_level + a.g.nspecial) * a.ncoeff;   // one key component
+    const T* key = (const T*)a.ksk + (uint64_t)krow * a.ncoeff + c;
+    const T* rp = (const T*)a.raised + (uint64_t)r * a.ncoeff + c;
+    T* op = (T*)a.acc + (uint64_t)r * a.ncoeff + c;
+    const uint64_t p0 = blockIdx.z * a.prun;
+    const uint64_t p1 = p0 + a.prun < a.npoly ? p0 + a.prun : a.npoly;
+    const uint64_t cstride = (uint64_t)rows * a.ncoeff;   // one component of acc
+
+    if (ND) {
+        constexpr int NK = ND ? ND : 1;
+        uint64_t k0[NK][V], k1[NK][V];
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            Lane<V>::load(key + (uint64_t)(2 * j) * kcs, k0[j]);
+            Lane<V>::load(key + (uint64_t)(2 * j + 1) * kcs, k1[j]);
+        }
+        for (uint64_t p = p0; p < p1; ++p) {
+            uint64_t x[NK][V];
+#pragma unroll
+            for (int j = 0; j < NK; ++j) Lane<V>::load(rp + (uint64_t)j * a.digit_stride + p * a.poly_stride, x[j]);
+            u128 s0[V], s1[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) s0[k] = s1[k] = 0;
+#pragma unroll
+            for (int j = 0; j < NK; ++j)
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    s0[k] += (u128)x[j][k] * k0[j][k];
+                    s1[k] += (u128)x[j][k] * k1[j][k];
+                }
+            uint64_t o0[V], o1[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                o0[k] = barrett128(s0[k], q, r0, r1);
+                o1[k] = barrett128(s1[k], q, r0, r1);
+            }
+            Lane<V>::store(op + p * a.acc_stride, o0);
+            Lane<V>::store(op + p * a.acc_stride + cstride, o1);
+        }
+    } else {
+        for (uint64_t p = p0; p < p1; ++p) {
+            uint64_t o0[V], o1[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) o0[k] = o1[k] = 0;
+            for (int j0 = 0; j0 < a.ndigits; j0 += 16) {   // 16 products < 2^124 and a residue < 2^62 fit a u128
+                u128 s0[V], s1[V];
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    s0[k] = o0[k];
+                    s1[k] = o1[k];
+                }
+                const int j1 = j0 + 16 < a.ndigits ? j0 + 16 : a.ndigits;
+                for (int j = j0; j < j1; ++j) {
+                    uint64_t x[V], ka[V], kb[V];
+                    Lane<V>::load(rp + (uint64_t)j * a.digit_stride + p * a.poly_stride, x);
+                    Lane<V>::load(key + (uint64_t)(2 * j) * kcs, ka);
+                    Lane<V>::load(key + (uint64_t)(2 * j + 1) * kcs, kb);
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        s0[k] += (u128)x[k] * ka[k];
+                        s1[k] += (u128)x[k] * kb[k];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    o0[k] = barrett128(s0[k], q, r0, r1);
+                    o1[k] = barrett128(s1[k], q, r0, r1);
+                }
+            }
+            Lane<V>::store(op + p * a.acc_stride, o0);
+            Lane<V>::store(op + p * a.acc_stride + cstride, o1);
+        }
+    }
+}
+
+// One thread per (digit j, key row r, coefficient): ksk[j][1][r] = a_j[r], ksk[j][0][r] = e_j[r] - a_j[r] s_to[r] +
+// F s_from[r] mod q_r, F = pmod[r] on the rows of digit j and 0 elsewhere (the special rows included).
+__global__ __launch_bounds__(256) void ksk_assemble_kernel(const uint64_t* __restrict__ s_from,
+                                                           const uint64_t* __restrict__ s_to,
+                                                           const uint64_t* __restrict__ av,
+                                                           const uint64_t* __restrict__ ev, uint64_t* __restrict__ ksk,
+                                                           int key_level, int key_rows, int alpha, int special_start,
+                                                           int logN, const uint64_t* __restrict__ pmod,
+                                                           const uint64_t* __restrict__ dmod, uint64_t total) {
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const uint64_t row = i >> logN, c = i & ((1ull << logN) - 1);
+    const uint64_t j = row / (uint64_t)key_rows, r = row - j * (uint64_t)key_rows;
+    const uint64_t limb = r < (uint64_t)key_level ? r : (uint64_t)special_start + r - key_level;
+    const uint64_t q = dmod[3 * limb], r0 = dmod[3 * limb + 1], r1 = dmod[3 * limb + 2];
+    const uint64_t F = (r < (uint64_t)key_level && r / (uint64_t)alpha == j) ? pmod[r] : 0;
+    const uint64_t sk = (r << logN) + c;
+    const uint64_t aa = av[i], as = barrett128((u128)aa * s_to[sk], q, r0, r1);
+    const uint64_t b = barrett128((u128)F * s_from[sk] + ev[i] + (q - as), q, r0, r1);
+    const uint64_t o = ((j * 2 * (uint64_t)key_rows + r) << logN) + c;
+    ksk[o] = b;
+    ksk[o + ((uint64_t)key_rows << logN)] = aa;
+}
+
+using KsipKernel = void (*)(KsipArgs, const uint64_t*);
+
+template <int V>
+static KsipKernel pick_ksip(int nd) {
+    switch (nd) {
+        case 1: return ksk_inner_product_kernel<1, V>;
+        case 2: return ksk_inner_product_kernel<2, V>;
+        case 3: return ksk_inner_product_kernel<3, V>;
+        case 4: return ksk_inner_product_kernel<4, V>;
+        case 5: return ksk_inner_product_kernel<5, V>;
+        case 6: return ksk_inner_product_kernel<6, V>;
+        default: return ksk_inner_product_kernel<0, V>;
+    }
+}
+static_assert(kKsipUnroll == 6, "pick_ksip lists the unrolled digit counts");
+
+int launch_ksk_inner_product(mfhe_ctx* c, KsipArgs a, hipStream_t st) {
+    if (a.npoly == 0 || a.ncoeff == 0) return MFHE_OK;
+    const bool wide = a.ncoeff % 2 == 0 && a.digit_stride % 2 == 0 && a.poly_stride % 2 == 0 && a.acc_stride % 2 == 0 &&
+                      (((uintptr_t)a.raised | (uintptr_t)a.ksk | (uintptr_t)a.acc) & 15) == 0;
+    if (wide) {
+        a.ncoeff /= 2;
+        a.digit_stride /= 2;
+        a.poly_stride /= 2;
+        a.acc_stride /= 2;
+    }
+    const uint32_t block = a.ncoeff >= 256 ? 256 : (uint32_t)((a.ncoeff + 63) / 64 * 64);
+    const uint64_t bx = (a.ncoeff + block - 1) / block;
+    const uint64_t rows = (uint64_t)a.g.rows();
+    if (bx > 0x7fffffffull || rows > 65535) return set_error(MFHE_EINVAL, "ksk_inner_product: too large for one launch");
+    // A thread keeps its key slice across `prun` polynomials: as long a run as still leaves about 4096 workgroups
+    // (16 per CU) in the grid, and never shorter than kKsipMinRun (or the batch).
+    uint64_t runs = 4096 / (bx * rows);
+    runs = runs < 1 ? 1 : runs;
+    a.prun = (a.npoly + runs - 1) / runs;
+    if (a.prun < kKsipMinRun) a.prun = a.npoly < kKsipMinRun ? a.npoly : kKsipMinRun;
+    if ((a.npoly + a.prun - 1) / a.prun > 65535) a.prun = (a.npoly + 65534) / 65535;   // grid z limit
+    runs = (a.npoly + a.prun - 1) / a.prun;
+    const KsipKernel k = wide ? pick_ksip<2>(a.ndigits) : pick_ksip<1>(a.ndigits);
+    hipLaunchKernelGGL(k, dim3((uint32_t)bx, (uint32_t)rows, (uint32_t)runs), dim3(block), 0, st, a,
+                       (const uint64_t*)c->d_dmod);
+    MFHE_CHECK_LAUNCH("ksk_inner_product_kernel");
+    return MFHE_OK;
+}
+
+// [key_level] P mod q_r, cached per (key_level, special range); built and uploaded on first use
+static int ksk_pmod_table(mfhe_ctx* c, int key_level, int sp, int nsp, const uint64_t** tab) {
+    std::lock_guard<std::mutex> lock(c->bconv_mu);
+    for (const auto& e : c->ksk_tabs)
+        if (e.key_level == key_level && e.special_start == sp && e.nspecial == nsp) {
+            *tab = e.d_pmod;
+            return MFHE_OK;
+        }
+    std::vector<uint64_t> h(key_level);
+    for (int r = 0; r < key_level; ++r) {
+        const uint64_t q = c->moduli[r];
+        uint64_t v = 1 % q;
+        for (int k = 0; k < nsp; ++k) v = hm::mulmod(v, c->moduli[sp + k] % q, q);
+        h[r] = v;
+    }
+    void* d = nullptr;
+    MFHE_HIP(hipMalloc(&d, h.size() * 8));
+    hipError_t e = hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_error(e, "hipMemcpy (switching key table)");
+    }
+    c->allocs.push_back(d);
+    c->ksk_tabs.push_back({key_level, sp, nsp, (uint64_t*)d});
+    *tab = (const uint64_t*)d;
+    return MFHE_OK;
+}
+
+// ---- argument checks (nothing here touches the device) ----
+static int check_ctx(const mfhe_ctx* c) {
+    if (!c) return set_error(MFHE_EINVAL, "null ctx");
+    if (!(c->conv & MFHE_CONV_PHANTOM)) return set_error(MFHE_ENOTREADY, "context was created without MFHE_CONV_PHANTOM");
+    return MFHE_OK;
+}
+
+static int check_geom(const mfhe_ctx* c, const KsGeom& g, const char* what) {
+    const std::string w(what);
+    if (g.nspecial < 1) return set_error(MFHE_EINVAL, w + ": nspecial < 1");
+    if (g.key_level < 1 || g.key_level > c->L) return set_error(MFHE_EINVAL, w + ": key_level outside the context");
+    if (g.level < 1) return set_error(MFHE_EINVAL, w + ": level < 1");
+    if (g.level > g.key_level) return set_error(MFHE_EINVAL, w + ": level > key_level");
+    if (g.special_start < g.key_level) return set_error(MFHE_EINVAL, w + ": special limbs overlap [0, key_level)");
+    if (g.special_start > c->L || g.nspecial > c->L - g.special_start)
+        return set_error(MFHE_EINVAL, w + ": special limbs outside the context");
+    return MFHE_OK;
+}
+
+// words spanned by npoly blocks of `words` words, `stride` apart
+static size_t span(size_t npoly, size_t stride, size_t words) { return npoly ? (npoly - 1) * stride + words : 0; }
+static bool ranges_overlap(const uint64_t* a, size_t na, const uint64_t* b, size_t nb) {
+    return na && nb && a < b + nb && b < a + na;
+}
+
+// words of the key switch's block of the workspace: raised digits, acc, the inner calls' scratch (the ModDown of both
+// components at once: 2 npoly polynomials)
+static size_t ks_ws_words(size_t npoly, int beta, size_t rows, size_t N) { return ((size_t)beta + 4) * npoly * rows * N; }
+
+}  // namespace mfhe
+
+using namespace mfhe;
+
+#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
+
+extern "C" int mfhe_ksk_assemble(mfhe_ctx* c, const uint64_t* d_s_from, const uint64_t* d_s_to, const uint64_t* d_a,
+                                 const uint64_t* d_e, uint64_t* d_ksk, int key_level, int alpha, int special_start,
+                                 int nspecial, mfhe_stream_t s) {
+    RC(check_ctx(c));
+    if (!d_s_from || !d_s_to || !d_a || !d_e || !d_ksk) return set_error(MFHE_EINVAL, "ksk_assemble: null pointer");
+    if (alpha < 1) return set_error(MFHE_EINVAL, "ksk_assemble: alpha < 1");
+    const KsGeom g{key_level, key_level, special_start, nspecial};
+    RC(check_geom(c, g, "ksk_assemble"));
+    const uint64_t* pmod = nullptr;
+    RC(ksk_pmod_table(c, key_level, special_start, nspecial, &pmod));
+    const int beta = (key_level + alpha - 1) / alpha;
+    const uint64_t total = (uint64_t)beta * g.key_rows() * c->N;
+    const uint64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffull) return set_error(MFHE_EINVAL, "ksk_assemble: too many coefficients for one launch");
+    hipLaunchKernelGGL(ksk_assemble_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)s, d_s_from, d_s_to, d_a,
+                       d_e, d_ksk, key_level, g.key_rows(), alpha, special_start, c->logN, pmod,
+                       (const uint64_t*)c->d_dmod, total);
+    MFHE_CHECK_LAUNCH("ksk_assemble_kernel");
+    return MFHE_OK;
+}
+
+extern "C" int mfhe_ksk_inner_product(mfhe_ctx* c, const uint64_t* d_raised, size_t digit_stride, size_t poly_stride,
+                                      const uint64_t* d_ksk, uint64_t* d_acc, size_t acc_poly_stride, size_t npoly,
+                                      int ndigits, int level, int key_level, int special_start, int nspecial,
+                                      mfhe_stream_t s) {
+    RC(check_ctx(c));
+    if (!d_raised || !d_ksk || !d_acc) return set_error(MFHE_EINVAL, "ksk_inner_product: null pointer");
+    if (ndigits < 1) return set_error(MFHE_EINVAL, "ksk_inner_product: ndigits < 1");
+    const KsGeom g{level, key_level, special_start, nspecial};
+    RC(check_geom(c, g, "ksk_inner_product"));
+    const size_t N = c->N, rows = (size_t)g.rows();
+    if (poly_stride / N < rows || acc_poly_stride / N < 2 * rows)
+        return set_error(MFHE_EINVAL, "ksk_inner_product: poly stride smaller than rows * N");
+    if (npoly && digit_stride < span(npoly, poly_stride, rows * N))
+        return set_error(MFHE_EINVAL, "ksk_inner_product: digit stride smaller than the polynomials of a digit");
+    KsipArgs a{};
+    a.raised = d_raised; a.ksk = d_ksk; a.acc = d_acc;
+    a.digit_stride = digit_stride; a.poly_stride = poly_stride; a.acc_stride = acc_poly_stride;
+    a.ncoeff = N; a.npoly = npoly; a.ndigits = ndigits; a.g = g;
+    return launch_ksk_inner_product(c, a, (hipStream_t)s);
+}
+
+// the tables of one key switch geometry: per digit the ModUp plan with its tables, and ModDown's
+struct KsTables {
+    std::vector<ModUpPlan> plan;
+    std::vector<const uint64_t*> tab;   // [beta][3]
+    const uint64_t* down = nullptr;
+    int beta = 0;
+};
+static int ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t) {
+    t.beta = (g.level + alpha - 1) / alpha;
+    t.plan.assign(t.beta, ModUpPlan{});
+    t.tab.assign((size_t)3 * t.beta, nullptr);
+    for (int j = 0; j < t.beta; ++j) {
+        const int ds = j * alpha, dc = g.level - ds < alpha ? g.level - ds : alpha;
+        RC(check_modup(c, g.level, ds, dc, g.special_start, g.nspecial, t.plan[j]));
+        RC(ntt_modup_tables(c, ds, dc, t.plan[j], &t.tab[(size_t)3 * j]));
+    }
+    return bconv_table(c, g.special_start, g.nspecial, 0, g.level, &t.down);
+}
+
+extern "C" int mfhe_keyswitch_reserve(mfhe_ctx* c, size_t npoly, int level, int key_level, int alpha,
+                                      int special_start, int nspecial) {
+    RC(check_ctx(c));
+    if (alpha < 1) return set_error(MFHE_EINVAL, "keyswitch_reserve: alpha < 1");
+    const KsGeom g{level, key_level, special_start, nspecial};
+    RC(check_geom(c, g, "keyswitch_reserve"));
+    KsTables t;
+    RC(ks_tables(c, g, alpha, t));
+    return grow_ws(c, ks_ws_words(npoly, t.beta, (size_t)g.rows(), c->N) * 8);
+}
+
+extern "C" int mfhe_keyswitch(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const uint64_t* d_ksk,
+                              uint64_t* d_out0, uint64_t* d_out1, size_t out_stride, size_t npoly, int level,
+                              int key_level, int alpha, int special_start, int nspecial, int flags, mfhe_stream_t s) {
+    RC(check_ctx(c));
+    if (!d_in || !d_ksk || !d_out0 || !d_out1) return set_error(MFHE_EINVAL, "keyswitch: null pointer");
+    if (alpha < 1) return set_error(MFHE_EINVAL, "keyswitch: alpha < 1");
+    if (flags & ~MFHE_KS_ADD) return set_error(MFHE_EINVAL, "keyswitch: unknown flag");
+    const KsGeom g{level, key_level, special_start, nspecial};
+    RC(check_geom(c, g, "keyswitch"));
+    const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
+    if (in_stride < lw || out_stride < lw) return set_error(MFHE_EINVAL, "keyswitch: poly stride smaller than level * N");
+    const size_t isp = span(npoly, in_stride, lw), osp = span(npoly, out_stride, lw);
+    if (ranges_overlap(d_in, isp, d_out0, osp) || ranges_overlap(d_in, isp, d_out1, osp))
+        return set_error(MFHE_EINVAL, "keyswitch: the input overlaps an output");
+    if (ranges_overlap(d_out0, osp, d_out1, osp)) return set_error(MFHE_EINVAL, "keyswitch: the outputs overlap");
+    if (npoly == 0) return MFHE_OK;
+    // every table and the workspace before the first launch (nothing to do after mfhe_keyswitch_reserve)
+    KsTables t;
+    RC(ks_tables(c, g, alpha, t));
+    RC(grow_ws(c, ks_ws_words(npoly, t.beta, rows, N) * 8));
+    hipStream_t st = (hipStream_t)s;
+    const size_t pw = rows * N;                                   // one raised polynomial
+    uint64_t* raised = (uint64_t*)c->ws;                          // [beta][npoly][rows][N]
+    uint64_t* acc = raised + (size_t)t.beta * npoly * pw;         // [npoly][2][rows][N]
+    uint64_t* scratch = acc + 2 * npoly * pw;                     // 2 npoly * rows * N words
+    for (int j = 0; j < t.beta; ++j) {
+        const int ds = j * alpha, dc = level - ds < alpha ? level - ds : alpha;
+        RC(ntt_modup_body(c, d_in, in_stride, raised + (size_t)j * npoly * pw, pw, npoly, ds, dc, t.plan[j],
+                          &t.tab[(size_t)3 * j], scratch, st));
+    }
+    KsipArgs a{};
+    a.raised = raised; a.ksk = d_ksk; a.acc = acc;
+    a.digit_stride = npoly * pw; a.poly_stride = pw; a.acc_stride = 2 * pw;
+    a.ncoeff = N; a.npoly = npoly; a.ndigits = t.beta; a.g = g;
+    RC(launch_ksk_inner_product(c, a, st));
+    // ModDown of both components as one batch of 2 npoly polynomials, then one tail per component
+    const uint64_t* cen = nullptr;
+    RC(ntt_moddown_center(c, acc, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
+    uint64_t* outs[2] = {d_out0, d_out1};
+    for (int k = 0; k < 2; ++k)
+        RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_stride,
+                            (flags & MFHE_KS_ADD) ? outs[k] : nullptr, npoly, level, nspecial, t.down, st));
+    return MFHE_OK;
+}

@@ -191,6 +191,13 @@ struct mfhe_ctx {
     };
     std::vector<BconvEntry> bconv;
     std::mutex bconv_mu;
+    // switching-key assembly constants (keyswitch.hip), one device table per (key_level, special range):
+    // [key_level] P mod q_r, P the product of the special moduli; owned by allocs, guarded by bconv_mu
+    struct KskEntry {
+        int key_level, special_start, nspecial;
+        uint64_t* d_pmod;
+    };
+    std::vector<KskEntry> ksk_tabs;
 
     std::vector<void*> allocs;  // everything above, freed at destroy
 };

@@ -28,6 +28,7 @@ OPT_NTT_FUSED, OPT_WCRT_MFMA = 6, 9   # OPT_NTT_FUSED: removed in r04, only 0 ac
 OPT_CGEMM_MFMA, OPT_HE_FUSED, OPT_TRACE_SPLIT = 10, 11, 12
 XCHG_ALLGATHER, XCHG_ALLTOALL = 0, 1
 BCONV_FAST, BCONV_CENTERED = 0, 1
+KS_ADD = 1                      # keyswitch: add the results to what out0 / out1 hold (relinearisation)
 RECOMBINE_ROWS_GLOBAL = 1
 RECOMBINE_EXCHANGE_ONLY = 2     # measurement: exchanges only, composes skipped (out untouched)
 RECOMBINE_AFTER_PREV = 4        # the shard was complete when the previous chunked call on the comm was entered
@@ -120,6 +121,10 @@ _sig("mfhe_rns_modup", [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _in
 _sig("mfhe_ntt_bconv_reserve", [_vp, _sz, _int])
 _sig("mfhe_ntt_modup", [_vp, _vp, _sz, _vp, _sz, _sz, _int, _int, _int, _int, _int, _vp])
 _sig("mfhe_ntt_moddown", [_vp, _vp, _sz, _vp, _sz, _sz, _int, _int, _int, _vp])
+_sig("mfhe_ksk_assemble", [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp])
+_sig("mfhe_ksk_inner_product", [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_keyswitch_reserve", [_vp, _sz, _int, _int, _int, _int, _int])
+_sig("mfhe_keyswitch", [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -494,6 +499,90 @@ class Context:
         check(lib.mfhe_ntt_moddown(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, keep_count, drop_start,
                                    drop_count, _stream_ptr(stream)), "ntt_moddown")
         return dst
+
+    # ---- hybrid key switching (include/mfhe.h): evaluation domain, Q limbs [0, level), K special limbs from
+    # special_start (>= key_level); a (level + K)-row block has limb r on row r < level, else special_start + r - level
+    def ksk_assemble(self, s_from, s_to, a, e, ksk, key_level, alpha, special_start, nspecial, stream=None):
+        """ksk [beta][2][key_level + K][N] from s_from, s_to [key_level + K][N] and a, e [beta][key_level + K][N]:
+        component 1 = a_j, component 0 = e_j - a_j s_to + F s_from (F = P mod q_r on the rows of digit j, else 0)."""
+        rows, beta = key_level + nspecial, -(-key_level // max(alpha, 1))
+        for t, what in ((s_from, "s_from"), (s_to, "s_to")):
+            self._need_polys(t, 1, rows * self.N, rows, self.N, f"ksk_assemble {what}")
+        for t, what in ((a, "a"), (e, "e")):
+            self._need_polys(t, beta, rows * self.N, rows, self.N, f"ksk_assemble {what}")
+        self._need_polys(ksk, beta, 2 * rows * self.N, 2 * rows, self.N, "ksk_assemble ksk")
+        check(lib.mfhe_ksk_assemble(self._h, _ptr(s_from), _ptr(s_to), _ptr(a), _ptr(e), _ptr(ksk), key_level, alpha,
+                                    special_start, nspecial, _stream_ptr(stream)), "ksk_assemble")
+        return ksk
+
+    def ksk_inner_product(self, raised, ksk, acc, npoly, ndigits, level, key_level, special_start, nspecial,
+                          digit_stride=None, poly_stride=None, acc_stride=None, stream=None):
+        """acc [npoly][2][level + K][N] = sum over the digits of raised [ndigits][npoly][level + K][N] times
+        ksk [ndigits][2][key_level + K][N] (key rows [0, level) and the special rows).  One launch."""
+        rows = level + nspecial
+        pst = rows * self.N if poly_stride is None else poly_stride
+        dst = npoly * pst if digit_stride is None else digit_stride
+        ast = 2 * rows * self.N if acc_stride is None else acc_stride
+        self._need_polys(raised, npoly, pst, rows, self.N, "ksk_inner_product raised (one digit)")
+        _need(raised, (ndigits - 1) * dst + (npoly - 1) * pst + rows * self.N if npoly and ndigits > 0 else 0,
+              "ksk_inner_product raised")
+        self._need_polys(ksk, ndigits, 2 * (key_level + nspecial) * self.N, 2 * (key_level + nspecial), self.N,
+                         "ksk_inner_product ksk")
+        self._need_polys(acc, npoly, ast, 2 * rows, self.N, "ksk_inner_product acc")
+        check(lib.mfhe_ksk_inner_product(self._h, _ptr(raised), dst, pst, _ptr(ksk), _ptr(acc), ast, npoly, ndigits,
+                                         level, key_level, special_start, nspecial, _stream_ptr(stream)),
+              "ksk_inner_product")
+        return acc
+
+    def keyswitch_reserve(self, npoly, level, key_level, alpha, special_start, nspecial):
+        """Grow the workspace and build every table of this geometry: keyswitch then allocates nothing."""
+        check(lib.mfhe_keyswitch_reserve(self._h, npoly, level, key_level, alpha, special_start, nspecial),
+              "keyswitch_reserve")
+
+    def keyswitch(self, src, ksk, out0, out1, npoly, level, key_level, alpha, special_start, nspecial, flags=0,
+                  in_stride=None, out_stride=None, stream=None):
+        """src [npoly][level][N] -> out0, out1 [npoly][level][N] with out0 + out1 s_to ~ src s_from for the key's
+        (s_from, s_to): ModUp of every digit, inner product, ModDown.  flags: KS_ADD adds to out0 / out1."""
+        ist = level * self.N if in_stride is None else in_stride
+        ost = level * self.N if out_stride is None else out_stride
+        beta = -(-key_level // max(alpha, 1))
+        self._need_polys(src, npoly, ist, level, self.N, "keyswitch src")
+        self._need_polys(out0, npoly, ost, level, self.N, "keyswitch out0")
+        self._need_polys(out1, npoly, ost, level, self.N, "keyswitch out1")
+        self._need_polys(ksk, beta, 2 * (key_level + nspecial) * self.N, 2 * (key_level + nspecial), self.N,
+                         "keyswitch ksk")
+        check(lib.mfhe_keyswitch(self._h, _ptr(src), ist, _ptr(ksk), _ptr(out0), _ptr(out1), ost, npoly, level,
+                                 key_level, alpha, special_start, nspecial, flags, _stream_ptr(stream)), "keyswitch")
+        return out0, out1
+
+    def relinearize(self, d2, rlk, d0, d1, npoly, level, key_level, alpha, special_start, nspecial, in_stride=None,
+                    out_stride=None, stream=None):
+        """(d0, d1) += keyswitch(d2) with the relinearisation key rlk (s_from = s^2, s_to = s): a degree-2
+        ciphertext (d0, d1, d2) becomes the degree-1 ciphertext (d0, d1) of the same message."""
+        return self.keyswitch(d2, rlk, d0, d1, npoly, level, key_level, alpha, special_start, nspecial, KS_ADD,
+                              in_stride, out_stride, stream)
+
+    def gen_switch_key(self, s_from, s_to, key_level, alpha, special_start, nspecial, generator=None, sigma=3.2):
+        """A switching key [beta][2][key_level + K][N] from s_from to s_to (both [key_level + K][N], evaluation
+        domain).  The randomness lives in PyTorch: a uniform per limb, e a rounded Gaussian of width sigma clipped
+        at 6 sigma, its residues taken on every row and forward-transformed; the arithmetic is mfhe_ksk_assemble."""
+        import torch
+        rows, beta, n = key_level + nspecial, -(-key_level // alpha), self.N
+        dev = s_from.device
+        limbs = list(range(key_level)) + list(range(special_start, special_start + nspecial))
+        a = torch.empty((beta, rows, n), dtype=torch.int64, device=dev)
+        for r, l in enumerate(limbs):
+            a[:, r, :] = torch.randint(0, self.moduli[l], (beta, n), generator=generator, device=dev, dtype=torch.int64)
+        g = torch.randn((beta, n), generator=generator, device=dev, dtype=torch.float64) * sigma
+        ei = torch.round(g.clamp(-6.0 * sigma, 6.0 * sigma)).to(torch.int64)
+        q = torch.tensor([self.moduli[l] for l in limbs], dtype=torch.int64, device=dev)
+        e = torch.remainder(ei[:, None, :], q[None, :, None])          # [beta][rows][N], coefficient domain
+        eq, ep = e[:, :key_level].contiguous(), e[:, key_level:].contiguous()
+        self.ntt_fwd(eq, beta, 0, key_level)
+        self.ntt_fwd(ep, beta, special_start, nspecial)
+        e = torch.cat((eq, ep), dim=1).contiguous()
+        ksk = torch.empty(beta * 2 * rows * n, dtype=torch.int64, device=dev)
+        return self.ksk_assemble(s_from, s_to, a, e, ksk, key_level, alpha, special_start, nspecial)
 
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
         """RCCL exchange of this rank's [npoly][L/G][ncoeff] residue shard + compose of its polynomial slice
