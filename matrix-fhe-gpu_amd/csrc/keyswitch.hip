@@ -17,12 +17,14 @@
 // (ndigits <= kKsipUnroll; longer keys are re-read per polynomial, from the cache).  Both components accumulate as
 // unreduced u128 sums (products of canonical residues of moduli < 2^62 are < 2^124, so 16 fit; longer sums reduce
 // every 16 terms) and end in one 128-bit Barrett reduction against d_dmod.  The row is the grid's y index, so the
-// modulus constants are wave-uniform scalar loads.
+// modulus constants are wave-uniform scalar loads.  The Galois forms (galois.hip) use the same kernel with the raised
+// digits read through the gather pi_g of galois.hpp, a template parameter.
 #include "keyswitch.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include "bconv.hpp"
+#include "galois.hpp"
 #include "host_math.hpp"
 #include "mod128.hpp"
 
@@ -33,13 +35,33 @@ constexpr int kKsipUnroll = 6;
 // shortest run of polynomials one thread walks with its key slice (the whole batch when it is smaller)
 constexpr uint64_t kKsipMinRun = 4;
 
+// A raised element (V words) as the thread uses it: the pair swapped when the Galois gather asks for it.
+template <int V, bool PERM>
+static __device__ __forceinline__ void load_raised(const typename Lane<V>::T* p, bool swap, uint64_t (&x)[V]) {
+    Lane<V>::load(p, x);
+    if constexpr (PERM && V == 2) {
+        const uint64_t lo = swap ? x[V - 1] : x[0], hi = swap ? x[0] : x[V - 1];
+        x[0] = lo;
+        x[V - 1] = hi;
+    }
+}
+
 // ND: digits (template-unrolled, the key slice in registers) or 0 (generic loop over a.ndigits); V: coefficients per
-// thread.  dmod is a __restrict__ kernel parameter, indexed by the block's row: scalar loads.
-template <int ND, int V>
+// thread.  dmod is a __restrict__ kernel parameter, indexed by the block's row: scalar loads.  PERM: the raised digits
+// are read through the Galois gather pi_g (galois.hpp) -- element pi(c), or the pair pi(2c) >> 1 swapped when pi(2c)
+// is odd; the index is computed once, before the polynomial loop, and the key and the output keep index c.
+template <int ND, int V, bool PERM>
 __global__ __launch_bounds__(256) void ksk_inner_product_kernel(KsipArgs a, const uint64_t* __restrict__ dmod) {
     using T = typename Lane<V>::T;
     const uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (c >= a.ncoeff) return;
+    uint64_t cs = c;        // where the raised digits are read
+    bool swap = false;
+    if constexpr (PERM) {
+        const uint32_t src = galois_perm_index((uint32_t)c * V, a.galois_elt, a.log_n);
+        cs = V == 2 ? src >> 1 : src;
+        swap = V == 2 && (src & 1u);
+    }
     const int r = blockIdx.y;
     const int level = a.g.level, rows = level + a.g.nspecial;
     const int limb = r < level ? r : a.g.special_start + r - level;
@@ -47,7 +69,7 @@ __global__ __launch_bounds__(256) void ksk_inner_product_kernel(KsipArgs a, cons
     const uint64_t q = dmod[3 * limb], r0 = dmod[3 * limb + 1], r1 = dmod[3 * limb + 2];
     const uint64_t kcs = (uint64_t)(a.g.key_level + a.g.nspecial) * a.ncoeff;   // one key component
     const T* key = (const T*)a.ksk + (uint64_t)krow * a.ncoeff + c;
-    const T* rp = (const T*)a.raised + (uint64_t)r * a.ncoeff + c;
+    const T* rp = (const T*)a.raised + (uint64_t)r * a.ncoeff + cs;
     T* op = (T*)a.acc + (uint64_t)r * a.ncoeff + c;
     const uint64_t p0 = blockIdx.z * a.prun;
     const uint64_t p1 = p0 + a.prun < a.npoly ? p0 + a.prun : a.npoly;
@@ -64,7 +86,8 @@ __global__ __launch_bounds__(256) void ksk_inner_product_kernel(KsipArgs a, cons
         for (uint64_t p = p0; p < p1; ++p) {
             uint64_t x[NK][V];
 #pragma unroll
-            for (int j = 0; j < NK; ++j) Lane<V>::load(rp + (uint64_t)j * a.digit_stride + p * a.poly_stride, x[j]);
+            for (int j = 0; j < NK; ++j)
+                load_raised<V, PERM>(rp + (uint64_t)j * a.digit_stride + p * a.poly_stride, swap, x[j]);
             u128 s0[V], s1[V];
 #pragma unroll
             for (int k = 0; k < V; ++k) s0[k] = s1[k] = 0;
@@ -99,7 +122,7 @@ __global__ __launch_bounds__(256) void ksk_inner_product_kernel(KsipArgs a, cons
                 const int j1 = j0 + 16 < a.ndigits ? j0 + 16 : a.ndigits;
                 for (int j = j0; j < j1; ++j) {
                     uint64_t x[V], ka[V], kb[V];
-                    Lane<V>::load(rp + (uint64_t)j * a.digit_stride + p * a.poly_stride, x);
+                    load_raised<V, PERM>(rp + (uint64_t)j * a.digit_stride + p * a.poly_stride, swap, x);
                     Lane<V>::load(key + (uint64_t)(2 * j) * kcs, ka);
                     Lane<V>::load(key + (uint64_t)(2 * j + 1) * kcs, kb);
 #pragma unroll
@@ -149,19 +172,38 @@ using KsipKernel = void (*)(KsipArgs, const uint64_t*);
 template <int V>
 static KsipKernel pick_ksip(int nd) {
     switch (nd) {
-        case 1: return ksk_inner_product_kernel<1, V>;
-        case 2: return ksk_inner_product_kernel<2, V>;
-        case 3: return ksk_inner_product_kernel<3, V>;
-        case 4: return ksk_inner_product_kernel<4, V>;
-        case 5: return ksk_inner_product_kernel<5, V>;
-        case 6: return ksk_inner_product_kernel<6, V>;
-        default: return ksk_inner_product_kernel<0, V>;
+        case 1: return ksk_inner_product_kernel<1, V, false>;
+        case 2: return ksk_inner_product_kernel<2, V, false>;
+        case 3: return ksk_inner_product_kernel<3, V, false>;
+        case 4: return ksk_inner_product_kernel<4, V, false>;
+        case 5: return ksk_inner_product_kernel<5, V, false>;
+        case 6: return ksk_inner_product_kernel<6, V, false>;
+        default: return ksk_inner_product_kernel<0, V, false>;
     }
 }
-static_assert(kKsipUnroll == 6, "pick_ksip lists the unrolled digit counts");
+// the instantiations that read the raised digits through a Galois gather
+template <int V>
+static KsipKernel pick_ksip_galois(int nd) {
+    switch (nd) {
+        case 1: return ksk_inner_product_kernel<1, V, true>;
+        case 2: return ksk_inner_product_kernel<2, V, true>;
+        case 3: return ksk_inner_product_kernel<3, V, true>;
+        case 4: return ksk_inner_product_kernel<4, V, true>;
+        case 5: return ksk_inner_product_kernel<5, V, true>;
+        case 6: return ksk_inner_product_kernel<6, V, true>;
+        default: return ksk_inner_product_kernel<0, V, true>;
+    }
+}
+static_assert(kKsipUnroll == 6, "pick_ksip and pick_ksip_galois list the unrolled digit counts");
 
 int launch_ksk_inner_product(mfhe_ctx* c, KsipArgs a, hipStream_t st) {
     if (a.npoly == 0 || a.ncoeff == 0) return MFHE_OK;
+    a.log_n = 0;
+    if (a.galois_elt) {   // the gather is defined on power-of-two rows, for an odd element below 2 N
+        while ((1ull << a.log_n) < a.ncoeff) ++a.log_n;
+        if ((1ull << a.log_n) != a.ncoeff || a.log_n > 30 || !(a.galois_elt & 1u) || a.galois_elt >= 2 * a.ncoeff)
+            return set_error(MFHE_EINVAL, "ksk_inner_product: Galois element is not an odd integer in [1, 2 N)");
+    }
     const bool wide = a.ncoeff % 2 == 0 && a.digit_stride % 2 == 0 && a.poly_stride % 2 == 0 && a.acc_stride % 2 == 0 &&
                       (((uintptr_t)a.raised | (uintptr_t)a.ksk | (uintptr_t)a.acc) & 15) == 0;
     if (wide) {
@@ -182,7 +224,8 @@ int launch_ksk_inner_product(mfhe_ctx* c, KsipArgs a, hipStream_t st) {
     if (a.prun < kKsipMinRun) a.prun = a.npoly < kKsipMinRun ? a.npoly : kKsipMinRun;
     if ((a.npoly + a.prun - 1) / a.prun > 65535) a.prun = (a.npoly + 65534) / 65535;   // grid z limit
     runs = (a.npoly + a.prun - 1) / a.prun;
-    const KsipKernel k = wide ? pick_ksip<2>(a.ndigits) : pick_ksip<1>(a.ndigits);
+    const KsipKernel k = a.galois_elt ? (wide ? pick_ksip_galois<2>(a.ndigits) : pick_ksip_galois<1>(a.ndigits))
+                                      : (wide ? pick_ksip<2>(a.ndigits) : pick_ksip<1>(a.ndigits));
     hipLaunchKernelGGL(k, dim3((uint32_t)bx, (uint32_t)rows, (uint32_t)runs), dim3(block), 0, st, a,
                        (const uint64_t*)c->d_dmod);
     MFHE_CHECK_LAUNCH("ksk_inner_product_kernel");
@@ -218,13 +261,13 @@ static int ksk_pmod_table(mfhe_ctx* c, int key_level, int sp, int nsp, const uin
 }
 
 // ---- argument checks (nothing here touches the device) ----
-static int check_ctx(const mfhe_ctx* c) {
+int ks_check_ctx(const mfhe_ctx* c) {
     if (!c) return set_error(MFHE_EINVAL, "null ctx");
     if (!(c->conv & MFHE_CONV_PHANTOM)) return set_error(MFHE_ENOTREADY, "context was created without MFHE_CONV_PHANTOM");
     return MFHE_OK;
 }
 
-static int check_geom(const mfhe_ctx* c, const KsGeom& g, const char* what) {
+int ks_check_geom(const mfhe_ctx* c, const KsGeom& g, const char* what) {
     const std::string w(what);
     if (g.nspecial < 1) return set_error(MFHE_EINVAL, w + ": nspecial < 1");
     if (g.key_level < 1 || g.key_level > c->L) return set_error(MFHE_EINVAL, w + ": key_level outside the context");
@@ -236,15 +279,21 @@ static int check_geom(const mfhe_ctx* c, const KsGeom& g, const char* what) {
     return MFHE_OK;
 }
 
+int ks_check_galois(const mfhe_ctx* c, int galois_elt, const char* what) {
+    if (galois_elt < 1 || !(galois_elt & 1) || (uint64_t)galois_elt >= 2 * (uint64_t)c->N)
+        return set_error(MFHE_EINVAL, std::string(what) + ": Galois element is not an odd integer in [1, 2 N)");
+    return MFHE_OK;
+}
+
 // words spanned by npoly blocks of `words` words, `stride` apart
-static size_t span(size_t npoly, size_t stride, size_t words) { return npoly ? (npoly - 1) * stride + words : 0; }
-static bool ranges_overlap(const uint64_t* a, size_t na, const uint64_t* b, size_t nb) {
+size_t ks_span(size_t npoly, size_t stride, size_t words) { return npoly ? (npoly - 1) * stride + words : 0; }
+bool ks_ranges_overlap(const uint64_t* a, size_t na, const uint64_t* b, size_t nb) {
     return na && nb && a < b + nb && b < a + na;
 }
 
 // words of the key switch's block of the workspace: raised digits, acc, the inner calls' scratch (the ModDown of both
 // components at once: 2 npoly polynomials)
-static size_t ks_ws_words(size_t npoly, int beta, size_t rows, size_t N) { return ((size_t)beta + 4) * npoly * rows * N; }
+size_t ks_ws_words(size_t npoly, int beta, size_t rows, size_t N) { return ((size_t)beta + 4) * npoly * rows * N; }
 
 }  // namespace mfhe
 
@@ -255,11 +304,11 @@ using namespace mfhe;
 extern "C" int mfhe_ksk_assemble(mfhe_ctx* c, const uint64_t* d_s_from, const uint64_t* d_s_to, const uint64_t* d_a,
                                  const uint64_t* d_e, uint64_t* d_ksk, int key_level, int alpha, int special_start,
                                  int nspecial, mfhe_stream_t s) {
-    RC(check_ctx(c));
+    RC(ks_check_ctx(c));
     if (!d_s_from || !d_s_to || !d_a || !d_e || !d_ksk) return set_error(MFHE_EINVAL, "ksk_assemble: null pointer");
     if (alpha < 1) return set_error(MFHE_EINVAL, "ksk_assemble: alpha < 1");
     const KsGeom g{key_level, key_level, special_start, nspecial};
-    RC(check_geom(c, g, "ksk_assemble"));
+    RC(ks_check_geom(c, g, "ksk_assemble"));
     const uint64_t* pmod = nullptr;
     RC(ksk_pmod_table(c, key_level, special_start, nspecial, &pmod));
     const int beta = (key_level + alpha - 1) / alpha;
@@ -273,35 +322,48 @@ extern "C" int mfhe_ksk_assemble(mfhe_ctx* c, const uint64_t* d_s_from, const ui
     return MFHE_OK;
 }
 
-extern "C" int mfhe_ksk_inner_product(mfhe_ctx* c, const uint64_t* d_raised, size_t digit_stride, size_t poly_stride,
-                                      const uint64_t* d_ksk, uint64_t* d_acc, size_t acc_poly_stride, size_t npoly,
-                                      int ndigits, int level, int key_level, int special_start, int nspecial,
-                                      mfhe_stream_t s) {
-    RC(check_ctx(c));
+// galois_elt 0: the plain product; else the raised digits are gathered through pi_g
+static int ksk_inner_product_checked(mfhe_ctx* c, const uint64_t* d_raised, size_t digit_stride, size_t poly_stride,
+                                     const uint64_t* d_ksk, uint64_t* d_acc, size_t acc_poly_stride, size_t npoly,
+                                     int ndigits, int level, int key_level, int special_start, int nspecial,
+                                     uint32_t galois_elt, mfhe_stream_t s) {
+    RC(ks_check_ctx(c));
     if (!d_raised || !d_ksk || !d_acc) return set_error(MFHE_EINVAL, "ksk_inner_product: null pointer");
     if (ndigits < 1) return set_error(MFHE_EINVAL, "ksk_inner_product: ndigits < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(check_geom(c, g, "ksk_inner_product"));
+    RC(ks_check_geom(c, g, "ksk_inner_product"));
     const size_t N = c->N, rows = (size_t)g.rows();
     if (poly_stride / N < rows || acc_poly_stride / N < 2 * rows)
         return set_error(MFHE_EINVAL, "ksk_inner_product: poly stride smaller than rows * N");
-    if (npoly && digit_stride < span(npoly, poly_stride, rows * N))
+    if (npoly && digit_stride < ks_span(npoly, poly_stride, rows * N))
         return set_error(MFHE_EINVAL, "ksk_inner_product: digit stride smaller than the polynomials of a digit");
     KsipArgs a{};
     a.raised = d_raised; a.ksk = d_ksk; a.acc = d_acc;
     a.digit_stride = digit_stride; a.poly_stride = poly_stride; a.acc_stride = acc_poly_stride;
-    a.ncoeff = N; a.npoly = npoly; a.ndigits = ndigits; a.g = g;
+    a.ncoeff = N; a.npoly = npoly; a.ndigits = ndigits; a.g = g; a.galois_elt = galois_elt;
     return launch_ksk_inner_product(c, a, (hipStream_t)s);
 }
 
-// the tables of one key switch geometry: per digit the ModUp plan with its tables, and ModDown's
-struct KsTables {
-    std::vector<ModUpPlan> plan;
-    std::vector<const uint64_t*> tab;   // [beta][3]
-    const uint64_t* down = nullptr;
-    int beta = 0;
-};
-static int ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t) {
+extern "C" int mfhe_ksk_inner_product(mfhe_ctx* c, const uint64_t* d_raised, size_t digit_stride, size_t poly_stride,
+                                      const uint64_t* d_ksk, uint64_t* d_acc, size_t acc_poly_stride, size_t npoly,
+                                      int ndigits, int level, int key_level, int special_start, int nspecial,
+                                      mfhe_stream_t s) {
+    return ksk_inner_product_checked(c, d_raised, digit_stride, poly_stride, d_ksk, d_acc, acc_poly_stride, npoly,
+                                     ndigits, level, key_level, special_start, nspecial, 0, s);
+}
+
+extern "C" int mfhe_ksk_inner_product_galois(mfhe_ctx* c, const uint64_t* d_raised, size_t digit_stride,
+                                             size_t poly_stride, const uint64_t* d_ksk, uint64_t* d_acc,
+                                             size_t acc_poly_stride, size_t npoly, int ndigits, int level,
+                                             int key_level, int special_start, int nspecial, int galois_elt,
+                                             mfhe_stream_t s) {
+    RC(ks_check_ctx(c));
+    RC(ks_check_galois(c, galois_elt, "ksk_inner_product_galois"));
+    return ksk_inner_product_checked(c, d_raised, digit_stride, poly_stride, d_ksk, d_acc, acc_poly_stride, npoly,
+                                     ndigits, level, key_level, special_start, nspecial, (uint32_t)galois_elt, s);
+}
+
+int mfhe::ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t) {
     t.beta = (g.level + alpha - 1) / alpha;
     t.plan.assign(t.beta, ModUpPlan{});
     t.tab.assign((size_t)3 * t.beta, nullptr);
@@ -315,10 +377,10 @@ static int ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t) {
 
 extern "C" int mfhe_keyswitch_reserve(mfhe_ctx* c, size_t npoly, int level, int key_level, int alpha,
                                       int special_start, int nspecial) {
-    RC(check_ctx(c));
+    RC(ks_check_ctx(c));
     if (alpha < 1) return set_error(MFHE_EINVAL, "keyswitch_reserve: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(check_geom(c, g, "keyswitch_reserve"));
+    RC(ks_check_geom(c, g, "keyswitch_reserve"));
     KsTables t;
     RC(ks_tables(c, g, alpha, t));
     return grow_ws(c, ks_ws_words(npoly, t.beta, (size_t)g.rows(), c->N) * 8);
@@ -327,18 +389,18 @@ extern "C" int mfhe_keyswitch_reserve(mfhe_ctx* c, size_t npoly, int level, int 
 extern "C" int mfhe_keyswitch(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const uint64_t* d_ksk,
                               uint64_t* d_out0, uint64_t* d_out1, size_t out_stride, size_t npoly, int level,
                               int key_level, int alpha, int special_start, int nspecial, int flags, mfhe_stream_t s) {
-    RC(check_ctx(c));
+    RC(ks_check_ctx(c));
     if (!d_in || !d_ksk || !d_out0 || !d_out1) return set_error(MFHE_EINVAL, "keyswitch: null pointer");
     if (alpha < 1) return set_error(MFHE_EINVAL, "keyswitch: alpha < 1");
     if (flags & ~MFHE_KS_ADD) return set_error(MFHE_EINVAL, "keyswitch: unknown flag");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(check_geom(c, g, "keyswitch"));
+    RC(ks_check_geom(c, g, "keyswitch"));
     const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
     if (in_stride < lw || out_stride < lw) return set_error(MFHE_EINVAL, "keyswitch: poly stride smaller than level * N");
-    const size_t isp = span(npoly, in_stride, lw), osp = span(npoly, out_stride, lw);
-    if (ranges_overlap(d_in, isp, d_out0, osp) || ranges_overlap(d_in, isp, d_out1, osp))
+    const size_t isp = ks_span(npoly, in_stride, lw), osp = ks_span(npoly, out_stride, lw);
+    if (ks_ranges_overlap(d_in, isp, d_out0, osp) || ks_ranges_overlap(d_in, isp, d_out1, osp))
         return set_error(MFHE_EINVAL, "keyswitch: the input overlaps an output");
-    if (ranges_overlap(d_out0, osp, d_out1, osp)) return set_error(MFHE_EINVAL, "keyswitch: the outputs overlap");
+    if (ks_ranges_overlap(d_out0, osp, d_out1, osp)) return set_error(MFHE_EINVAL, "keyswitch: the outputs overlap");
     if (npoly == 0) return MFHE_OK;
     // every table and the workspace before the first launch (nothing to do after mfhe_keyswitch_reserve)
     KsTables t;

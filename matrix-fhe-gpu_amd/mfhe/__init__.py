@@ -125,6 +125,14 @@ _sig("mfhe_ksk_assemble", [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int,
 _sig("mfhe_ksk_inner_product", [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _vp])
 _sig("mfhe_keyswitch_reserve", [_vp, _sz, _int, _int, _int, _int, _int])
 _sig("mfhe_keyswitch", [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_ntt_automorphism", [_vp, _vp, _sz, _vp, _sz, _sz, _int, _int, _vp])
+_sig("mfhe_ksk_inner_product_galois",
+     [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_keyswitch_raise", [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _int, _int, _int, _int, _vp])
+_sig("mfhe_galois_apply_raised",
+     [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_galois_apply", [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_galois_reserve", [_vp, _sz, _int, _int, _int, _int, _int])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -584,6 +592,109 @@ class Context:
         ksk = torch.empty(beta * 2 * rows * n, dtype=torch.int64, device=dev)
         return self.ksk_assemble(s_from, s_to, a, e, ksk, key_level, alpha, special_start, nspecial)
 
+    # ---- Galois automorphisms and hoisted rotations (include/mfhe.h): the geometry of the key switch; a Galois
+    # element is an odd integer in [1, 2N) (galois_elt / galois_conj below)
+    def automorphism(self, src, dst, npoly, rows, galois_elt, in_stride=None, out_stride=None, stream=None):
+        """dst [npoly][rows][N] = sigma_g(src) in the evaluation domain: dst[p][r][i] = src[p][r][pi_g(i)].  Out of
+        place, one launch."""
+        ist = rows * self.N if in_stride is None else in_stride
+        ost = rows * self.N if out_stride is None else out_stride
+        self._need_polys(src, npoly, ist, rows, self.N, "automorphism src")
+        self._need_polys(dst, npoly, ost, rows, self.N, "automorphism dst")
+        check(lib.mfhe_ntt_automorphism(self._h, _ptr(src), ist, _ptr(dst), ost, npoly, rows, galois_elt,
+                                        _stream_ptr(stream)), "automorphism")
+        return dst
+
+    def _need_raised(self, raised, npoly, ndigits, rows, dst, pst, what):
+        self._need_polys(raised, npoly, pst, rows, self.N, f"{what} raised (one digit)")
+        _need(raised, (ndigits - 1) * dst + (npoly - 1) * pst + rows * self.N if npoly and ndigits > 0 else 0,
+              f"{what} raised")
+
+    def ksk_inner_product_galois(self, raised, ksk, acc, npoly, ndigits, level, key_level, special_start, nspecial,
+                                 galois_elt, digit_stride=None, poly_stride=None, acc_stride=None, stream=None):
+        """ksk_inner_product with the raised digits read through the gather of sigma_g:
+        acc[p][c][r][i] = sum_j raised[j][p][r][pi_g(i)] ksk[j][c][keyrow(r)][i].  One launch."""
+        rows = level + nspecial
+        pst = rows * self.N if poly_stride is None else poly_stride
+        dst = npoly * pst if digit_stride is None else digit_stride
+        ast = 2 * rows * self.N if acc_stride is None else acc_stride
+        self._need_raised(raised, npoly, ndigits, rows, dst, pst, "ksk_inner_product_galois")
+        self._need_polys(ksk, ndigits, 2 * (key_level + nspecial) * self.N, 2 * (key_level + nspecial), self.N,
+                         "ksk_inner_product_galois ksk")
+        self._need_polys(acc, npoly, ast, 2 * rows, self.N, "ksk_inner_product_galois acc")
+        check(lib.mfhe_ksk_inner_product_galois(self._h, _ptr(raised), dst, pst, _ptr(ksk), _ptr(acc), ast, npoly,
+                                                ndigits, level, key_level, special_start, nspecial, galois_elt,
+                                                _stream_ptr(stream)), "ksk_inner_product_galois")
+        return acc
+
+    def galois_reserve(self, npoly, level, key_level, alpha, special_start, nspecial):
+        """Grow the workspace and build every table of this geometry: keyswitch_raise, galois_apply_raised and
+        galois_apply then allocate nothing."""
+        check(lib.mfhe_galois_reserve(self._h, npoly, level, key_level, alpha, special_start, nspecial),
+              "galois_reserve")
+
+    def keyswitch_raise(self, src, raised, npoly, level, alpha, special_start, nspecial, in_stride=None,
+                        digit_stride=None, poly_stride=None, stream=None):
+        """The hoisted part of a rotation: raised [beta][npoly][level + K][N] = the ModUp of every digit of src
+        [npoly][level][N], as keyswitch raises them.  No key, no Galois element."""
+        rows, beta = level + nspecial, -(-level // max(alpha, 1))
+        ist = level * self.N if in_stride is None else in_stride
+        pst = rows * self.N if poly_stride is None else poly_stride
+        dst = npoly * pst if digit_stride is None else digit_stride
+        self._need_polys(src, npoly, ist, level, self.N, "keyswitch_raise src")
+        self._need_raised(raised, npoly, beta, rows, dst, pst, "keyswitch_raise")
+        check(lib.mfhe_keyswitch_raise(self._h, _ptr(src), ist, _ptr(raised), dst, pst, npoly, level, alpha,
+                                       special_start, nspecial, _stream_ptr(stream)), "keyswitch_raise")
+        return raised
+
+    def galois_apply_raised(self, c0, raised, gk, out0, out1, npoly, level, key_level, alpha, special_start, nspecial,
+                            galois_elt, in_stride=None, digit_stride=None, poly_stride=None, out_stride=None,
+                            stream=None):
+        """(out0, out1) = (sigma_g(c0) + k0, k1) from c0 [npoly][level][N], the raised digits of c1 (keyswitch_raise)
+        and the Galois key gk of g: out0 + out1 s ~ sigma_g(c0 + c1 s).  raised is only read."""
+        rows, beta = level + nspecial, -(-level // max(alpha, 1))
+        ist = level * self.N if in_stride is None else in_stride
+        ost = level * self.N if out_stride is None else out_stride
+        pst = rows * self.N if poly_stride is None else poly_stride
+        dst = npoly * pst if digit_stride is None else digit_stride
+        self._need_polys(c0, npoly, ist, level, self.N, "galois_apply_raised c0")
+        self._need_raised(raised, npoly, beta, rows, dst, pst, "galois_apply_raised")
+        self._need_polys(out0, npoly, ost, level, self.N, "galois_apply_raised out0")
+        self._need_polys(out1, npoly, ost, level, self.N, "galois_apply_raised out1")
+        self._need_polys(gk, -(-key_level // max(alpha, 1)), 2 * (key_level + nspecial) * self.N,
+                         2 * (key_level + nspecial), self.N, "galois_apply_raised gk")
+        check(lib.mfhe_galois_apply_raised(self._h, _ptr(c0), ist, _ptr(raised), dst, pst, _ptr(gk), _ptr(out0),
+                                           _ptr(out1), ost, npoly, level, key_level, alpha, special_start, nspecial,
+                                           galois_elt, _stream_ptr(stream)), "galois_apply_raised")
+        return out0, out1
+
+    def galois_apply(self, c0, c1, gk, out0, out1, npoly, level, key_level, alpha, special_start, nspecial, galois_elt,
+                     in_stride=None, out_stride=None, stream=None):
+        """One rotation or conjugation of the ciphertext (c0, c1), each [npoly][level][N], with the Galois key gk of
+        g: keyswitch_raise(c1) into the workspace, then galois_apply_raised."""
+        ist = level * self.N if in_stride is None else in_stride
+        ost = level * self.N if out_stride is None else out_stride
+        beta = -(-key_level // max(alpha, 1))
+        for t, what in ((c0, "c0"), (c1, "c1")):
+            self._need_polys(t, npoly, ist, level, self.N, f"galois_apply {what}")
+        for t, what in ((out0, "out0"), (out1, "out1")):
+            self._need_polys(t, npoly, ost, level, self.N, f"galois_apply {what}")
+        self._need_polys(gk, beta, 2 * (key_level + nspecial) * self.N, 2 * (key_level + nspecial), self.N,
+                         "galois_apply gk")
+        check(lib.mfhe_galois_apply(self._h, _ptr(c0), _ptr(c1), ist, _ptr(gk), _ptr(out0), _ptr(out1), ost, npoly,
+                                    level, key_level, alpha, special_start, nspecial, galois_elt,
+                                    _stream_ptr(stream)), "galois_apply")
+        return out0, out1
+
+    def gen_galois_key(self, s, galois_elt, key_level, alpha, special_start, nspecial, generator=None, sigma=3.2):
+        """The Galois key of g for the secret s [key_level + K][N] (evaluation domain): a switching key from
+        sigma_g(s) to s (gen_switch_key)."""
+        import torch
+        rows = key_level + nspecial
+        s_from = torch.empty(rows * self.N, dtype=torch.int64, device=s.device)
+        self.automorphism(s, s_from, 1, rows, galois_elt)
+        return self.gen_switch_key(s_from, s, key_level, alpha, special_start, nspecial, generator, sigma)
+
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
         """RCCL exchange of this rank's [npoly][L/G][ncoeff] residue shard + compose of its polynomial slice
         (include/mfhe.h mfhe_crt_recombine_sharded); out: npoly/G * ncoeff f64."""
@@ -767,6 +878,17 @@ def inwt_1d(data, itw, itw_shoup, dmod, scalar, scalar_shoup, dim, coeff_modulus
 
 
 # ---- host/device array helpers (uint64 stored in int64 tensors) ----
+def galois_elt(step: int, log_n: int) -> int:
+    """The Galois element of a slot rotation by `step`: 5^step mod 2N (the inverse of 5 for negative steps)."""
+    m = 2 << log_n
+    return pow(5, step, m) if step >= 0 else pow(pow(5, -1, m), -step, m)
+
+
+def galois_conj(log_n: int) -> int:
+    """The Galois element of the conjugation: 2N - 1."""
+    return (2 << log_n) - 1
+
+
 def to_device_u64(arr, device="cuda"):
     import numpy as np
     import torch
