@@ -302,6 +302,150 @@ def test_modup_scalar_variant_and_long_digit(mfhe, mixed_ctx):
     bo.check_pads()
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# every instantiation of bconv_kernel, and the generic loop's chunk boundaries
+#
+# pick_ns (csrc/bconv.hip) unrolls source counts 1 .. 8 and sends every longer source to a loop that reduces after
+# every 16 terms.  The tests above run 1, 2, 3 and 17; these run 4 .. 8, the first generic count 9, one full chunk
+# (16), two full chunks (32) and two chunks and one term (33), in all three modes the kernel has, in the 16-byte form
+# (ncoeff 258) and the scalar one (ncoeff 255), on more than one block.
+# ---------------------------------------------------------------------------------------------------------------
+SRC_COUNTS = [4, 5, 6, 7, 8, 9, 16, 32, 33]
+
+
+def _dst_range(src_count):
+    """Destination limbs (start, count): [17, 57) while the sources end below 17, else [33, 57)."""
+    return (17, 40) if src_count <= 17 else (33, 24)
+
+
+@pytest.mark.parametrize("src_count", SRC_COUNTS)
+def test_fast_conversion_every_source_count(mfhe, mixed_ctx, src_count):
+    import torch
+    mod = _mixed_moduli()
+    ds, dc = _dst_range(src_count)
+    src, dst = mod[:src_count], mod[ds:ds + dc]
+    rng = np.random.default_rng(1000 + src_count)
+    npoly = 3
+    for nc in (258, 255):
+        x = _random_residues(rng, npoly, src, nc)
+        tot = _fast_integer(x, src)
+        want = np.stack([(tot % int(d)).astype(np.uint64) for d in dst], axis=1)   # [3][dc][nc]
+        bi = _Buf(mfhe, npoly, src_count, nc, src_count * nc + 2, 0, x)
+        bo = _Buf(mfhe, npoly, dc, nc, dc * nc + 4)
+        mixed_ctx.rns_bconv(bi.t, bo.t, npoly, nc, 0, src_count, ds, dc, mfhe.BCONV_FAST, in_stride=bi.stride,
+                            out_stride=bo.stride)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(bo.blocks(), want, err_msg=f"nc={nc}")
+        bo.check_pads()
+        np.testing.assert_array_equal(bi.blocks(), x)   # input untouched
+
+
+@pytest.mark.parametrize("src_count", SRC_COUNTS)
+def test_centered_conversion_every_source_count(mfhe, mixed_ctx, src_count):
+    import torch
+    mod = _mixed_moduli()
+    ds, dc = _dst_range(src_count)
+    src, dst = mod[:src_count], mod[ds:ds + dc]
+    S = _prod(src)
+    npoly = 3
+    vals = [_centered_values(S, 258, 10 * src_count + p) for p in range(npoly)]
+    x = np.stack([_residues_of(v, src) for v in vals])
+    want = np.stack([_residues_of(v, dst) for v in vals])
+    for nc in (258, 255):
+        xs = np.ascontiguousarray(x[:, :, :nc])
+        bi = _Buf(mfhe, npoly, src_count, nc, src_count * nc + 2, 0, xs)
+        bo = _Buf(mfhe, npoly, dc, nc, dc * nc + 4)
+        mixed_ctx.rns_bconv(bi.t, bo.t, npoly, nc, 0, src_count, ds, dc, mfhe.BCONV_CENTERED, in_stride=bi.stride,
+                            out_stride=bo.stride)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(bo.blocks(), want[:, :, :nc], err_msg=f"nc={nc}")
+        bo.check_pads()
+        np.testing.assert_array_equal(bi.blocks(), xs)
+
+
+@pytest.mark.parametrize("nc", [258, 255])
+@pytest.mark.parametrize("drop_count", [4, 5, 8, 9, 17])
+def test_moddown_every_kind_of_drop_count(mfhe, mixed_ctx, drop_count, nc):
+    """Unrolled counts, the first generic count and the generic loop across its 16-term chunk; the dropped limbs
+    [17, 17 + drop_count) hold primes of 55, 50, 61, 35 and 20 bits.  Out of place and in place."""
+    _run_moddown(mfhe, mixed_ctx, 5, 17, drop_count, nc, 2, 100 * drop_count + nc)
+
+
+@pytest.mark.parametrize("nc", [258, 255])
+@pytest.mark.parametrize("digit_count", [4, 5, 8, 9])
+def test_modup_every_kind_of_digit_count(mfhe, mixed_ctx, digit_count, nc):
+    """A digit inside level 22, so destination rows lie on both sides of it, and 4 special limbs."""
+    import torch
+    mod = list(_mixed_moduli())
+    rng = np.random.default_rng(50 + digit_count)
+    level, ds, sp, nsp, npoly = 22, 2, 30, 4, 2
+    x = _random_residues(rng, npoly, mod[:level], nc)
+    want = _modup_want(x, mod, level, ds, digit_count, mod[sp:sp + nsp])
+    bi = _Buf(mfhe, npoly, level, nc, level * nc + 2, 0, x)
+    bo = _Buf(mfhe, npoly, level + nsp, nc, (level + nsp) * nc + 4)
+    mixed_ctx.rns_modup(bi.t, bo.t, npoly, nc, level, ds, digit_count, sp, nsp, in_stride=bi.stride,
+                        out_stride=bo.stride)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(bo.blocks(), want)
+    bo.check_pads()
+    np.testing.assert_array_equal(bi.blocks(), x)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the centred estimate at the documented limit
+#
+# include/mfhe.h promises the centred value for |x~| <= (1/2 - 2^-40) S.  m = floor(S/2) - ceil(S 2^-39) and m + 1 lie
+# inside that window with a factor of two to spare (S > 2^40 here), so x~ = +-m, +-(m - 1), +-(m + 1) must come out as
+# exactly x~ mod d_j: an f64 estimate that had lost ten of its bits would round some of them to the wrong multiple of S.
+# ---------------------------------------------------------------------------------------------------------------
+def _limit_values(S):
+    assert S > 1 << 40
+    m = S // 2 - -(-S // (1 << 39))
+    assert 2 * (m + 1) * (1 << 40) <= ((1 << 40) - 2) * S, "inside (1/2 - 2^-40) S"
+    return [m, -m, m - 1, -(m - 1), m + 1, -(m + 1)]
+
+
+@pytest.mark.parametrize("src_count", [1, 3, 8, 17, 33])
+def test_centered_conversion_exact_at_the_documented_limit(mfhe, mixed_ctx, src_count):
+    import torch
+    mod = _mixed_moduli()
+    ds, dc = (17, 11) if src_count <= 17 else (33, 24)
+    src, dst = mod[:src_count], mod[ds:ds + dc]
+    vals = _limit_values(_prod(src))
+    x, want = _residues_of(vals, src)[None], _residues_of(vals, dst)[None]
+    nc = len(vals)
+    for off in (0, 1):   # the 16-byte form, then (one word off) the scalar variant
+        bi = _Buf(mfhe, 1, src_count, nc, src_count * nc, off, x)
+        bo = _Buf(mfhe, 1, dc, nc, dc * nc + 2, off)
+        mixed_ctx.rns_bconv(bi.t, bo.t, 1, nc, 0, src_count, ds, dc, mfhe.BCONV_CENTERED, out_stride=bo.stride)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(bo.blocks(), want, err_msg=f"offset {off}")
+        bo.check_pads()
+
+
+@pytest.mark.parametrize("drop_count", [1, 3, 9])
+def test_moddown_exact_at_the_documented_limit(mfhe, mixed_ctx, drop_count):
+    """x = k P + r with the remainders r of _limit_values(P): round(x / P) = k on every kept limb."""
+    import torch
+    mod = _mixed_moduli()
+    keep_count, drop_start = 5, 17
+    keep, drop = mod[:keep_count], mod[drop_start:drop_start + drop_count]
+    P, Q = _prod(drop), _prod(keep)
+    rnd = random.Random(drop_count)
+    rs = _limit_values(P)
+    ks = [[0, 0, 1, 1, -1, -1], [rnd.randint(-(Q // 2), Q // 2) for _ in rs]]
+    x = np.stack([_residues_of([k * P + r for k, r in zip(kk, rs)], list(keep) + list(drop)) for kk in ks])
+    want = np.stack([_residues_of(kk, keep) for kk in ks])
+    nc, rows = len(rs), keep_count + drop_count
+    for off in (0, 1):
+        bi = _Buf(mfhe, 2, rows, nc, rows * nc, off, x)
+        bo = _Buf(mfhe, 2, keep_count, nc, keep_count * nc + 2, off)
+        mixed_ctx.rns_moddown(bi.t, bo.t, 2, nc, keep_count, drop_start, drop_count, out_stride=bo.stride)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(bo.blocks(), want, err_msg=f"offset {off}")
+        bo.check_pads()
+
+
 def _ntt_moduli(log_n, bits):
     return primes_of_size(bits[0], 2 << log_n, 5) + primes_of_size(bits[1], 2 << log_n, 2)
 
