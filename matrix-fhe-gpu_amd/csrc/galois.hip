@@ -121,9 +121,9 @@ extern "C" int mfhe_galois_reserve(mfhe_ctx* c, size_t npoly, int level, int key
 }
 
 // ModUp of every digit of d_in into raised [beta][npoly][rows][N] (strides in words); scratch: npoly rows N words
-static int raise_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* raised, size_t digit_stride,
-                      size_t poly_stride, size_t npoly, const KsGeom& g, int alpha, const KsTables& t,
-                      uint64_t* scratch, hipStream_t st) {
+int mfhe::raise_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* raised, size_t digit_stride,
+                     size_t poly_stride, size_t npoly, const KsGeom& g, int alpha, const KsTables& t,
+                     uint64_t* scratch, hipStream_t st) {
     for (int j = 0; j < t.beta; ++j) {
         const int ds = j * alpha, dc = g.level - ds < alpha ? g.level - ds : alpha;
         RC(ntt_modup_body(c, d_in, in_stride, raised + (size_t)j * digit_stride, poly_stride, npoly, ds, dc, t.plan[j],

@@ -233,7 +233,7 @@ int launch_ksk_inner_product(mfhe_ctx* c, KsipArgs a, hipStream_t st) {
 }
 
 // [key_level] P mod q_r, cached per (key_level, special range); built and uploaded on first use
-static int ksk_pmod_table(mfhe_ctx* c, int key_level, int sp, int nsp, const uint64_t** tab) {
+int ksk_pmod_table(mfhe_ctx* c, int key_level, int sp, int nsp, const uint64_t** tab) {
     std::lock_guard<std::mutex> lock(c->bconv_mu);
     for (const auto& e : c->ksk_tabs)
         if (e.key_level == key_level && e.special_start == sp && e.nspecial == nsp) {

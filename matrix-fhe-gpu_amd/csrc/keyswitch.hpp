@@ -57,4 +57,13 @@ struct KsTables {
 };
 int ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t);
 
+// ---- shared with lintrans.hip ----
+// [key_level] P mod q_r on the device, cached per (key_level, special range); built and uploaded on first use
+int ksk_pmod_table(mfhe_ctx* c, int key_level, int sp, int nsp, const uint64_t** tab);
+// galois.hip: ModUp of every digit of d_in into raised [beta][npoly][rows][N] (strides in words); scratch: npoly rows N
+// words
+int raise_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* raised, size_t digit_stride,
+               size_t poly_stride, size_t npoly, const KsGeom& g, int alpha, const KsTables& t, uint64_t* scratch,
+               hipStream_t st);
+
 }  // namespace mfhe

@@ -133,6 +133,26 @@ _sig("mfhe_galois_apply_raised",
      [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
 _sig("mfhe_galois_apply", [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
 _sig("mfhe_galois_reserve", [_vp, _sz, _int, _int, _int, _int, _int])
+
+
+class LtPlan(ctypes.Structure):
+    """mfhe_lt_plan (include/mfhe.h): host arrays, read during the call only."""
+    _fields_ = [
+        ("n_baby", _int), ("n_giant", _int), ("nterms", _int),
+        ("baby_elt", ctypes.POINTER(_int)), ("giant_elt", ctypes.POINTER(_int)),
+        ("d_gk_baby", ctypes.POINTER(_vp)), ("d_gk_giant", ctypes.POINTER(_vp)),
+        ("term_giant", ctypes.POINTER(_int)), ("term_baby", ctypes.POINTER(_int)),
+    ]
+
+
+LT_MAX_TERMS = 64               # lt_pt_mac: most terms of one sum (one giant step of a plan)
+_intp = ctypes.POINTER(_int)
+_sig("mfhe_lt_baby_step", [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _int, _int, _vp])
+_sig("mfhe_lt_pt_mac",
+     [_vp, _vp, _sz, _sz, _int, _vp, _sz, _int, _int, _vp, _sz, _intp, _intp, _int, _sz, _int, _int, _int, _vp])
+_sig("mfhe_lt_reserve", [_vp, _sz, _int, _int, _int, _int, _int, _int])
+_sig("mfhe_lt_apply", [_vp, ctypes.POINTER(LtPlan), _vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _sz, _sz, _int, _int, _int,
+                       _int, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -695,6 +715,95 @@ class Context:
         self.automorphism(s, s_from, 1, rows, galois_elt)
         return self.gen_switch_key(s_from, s, key_level, alpha, special_start, nspecial, generator, sigma)
 
+    # ---- encrypted linear transforms by baby-step giant-step (include/mfhe.h): the geometry of the key switch;
+    # bsgs_plan below splits rotation indices into the steps and terms these calls take
+    def lt_baby_step(self, c0, raised, gk, u, npoly, level, key_level, alpha, special_start, nspecial, galois_elt=1,
+                     in_stride=None, digit_stride=None, poly_stride=None, u_stride=None, stream=None):
+        """u [npoly][2][level + K][N] = the rotation of (c0, c1) by the Galois key gk of g, left in Q u P and scaled
+        by P (no ModDown): c0 [npoly][level][N], raised the raised digits of c1 (keyswitch_raise).  gk None with
+        galois_elt 1 is the unrotated term: `raised` is then c1 itself, laid out as c0."""
+        rows, beta = level + nspecial, -(-level // max(alpha, 1))
+        ist = level * self.N if in_stride is None else in_stride
+        pst = rows * self.N if poly_stride is None else poly_stride
+        dst = npoly * pst if digit_stride is None else digit_stride
+        ust = 2 * rows * self.N if u_stride is None else u_stride
+        self._need_polys(c0, npoly, ist, level, self.N, "lt_baby_step c0")
+        if gk is None:
+            self._need_polys(raised, npoly, ist, level, self.N, "lt_baby_step c1")
+        else:
+            self._need_raised(raised, npoly, beta, rows, dst, pst, "lt_baby_step")
+            self._need_polys(gk, -(-key_level // max(alpha, 1)), 2 * (key_level + nspecial) * self.N,
+                             2 * (key_level + nspecial), self.N, "lt_baby_step gk")
+        self._need_polys(u, npoly, ust, 2 * rows, self.N, "lt_baby_step u")
+        check(lib.mfhe_lt_baby_step(self._h, _ptr(c0), ist, _ptr(raised), dst, pst, _ptr(gk), _ptr(u), ust, npoly,
+                                    level, key_level, alpha, special_start, nspecial, galois_elt,
+                                    _stream_ptr(stream)), "lt_baby_step")
+        return u
+
+    def lt_pt_mac(self, u, pt, acc, term_u, term_pt, npoly, level, special_start, nspecial, nslots, npt,
+                  pt_level=None, slot_stride=None, poly_stride=None, pt_stride=None, acc_stride=None, stream=None):
+        """acc[p][c][r] = sum_t pt[term_pt[t]][ptrow(r)] u[term_u[t]][p][c][r] mod q_r: u [nslots][npoly][2][level + K][N],
+        pt [npt][pt_level + K][N] shared by the batch, acc [npoly][2][level + K][N]; term_u, term_pt Python lists of
+        1 .. 64 entries.  One launch."""
+        rows = level + nspecial
+        pt_level = level if pt_level is None else pt_level
+        pst = 2 * rows * self.N if poly_stride is None else poly_stride
+        sst = npoly * pst if slot_stride is None else slot_stride
+        tst = (pt_level + nspecial) * self.N if pt_stride is None else pt_stride
+        ast = 2 * rows * self.N if acc_stride is None else acc_stride
+        if len(term_u) != len(term_pt):
+            raise ValueError("lt_pt_mac: term_u and term_pt differ in length")
+        self._need_polys(u, npoly, pst, 2 * rows, self.N, "lt_pt_mac u (one slot)")
+        _need(u, (nslots - 1) * sst + (npoly - 1) * pst + 2 * rows * self.N if npoly and nslots > 0 else 0,
+              "lt_pt_mac u")
+        self._need_polys(pt, npt, tst, pt_level + nspecial, self.N, "lt_pt_mac pt")
+        self._need_polys(acc, npoly, ast, 2 * rows, self.N, "lt_pt_mac acc")
+        nt = len(term_u)
+        tu, tp = (_int * max(nt, 1))(*term_u), (_int * max(nt, 1))(*term_pt)
+        check(lib.mfhe_lt_pt_mac(self._h, _ptr(u), sst, pst, nslots, _ptr(pt), tst, npt, pt_level, _ptr(acc), ast, tu,
+                                 tp, nt, npoly, level, special_start, nspecial, _stream_ptr(stream)), "lt_pt_mac")
+        return acc
+
+    def lt_reserve(self, npoly, level, key_level, alpha, special_start, nspecial, n_baby):
+        """Grow the workspace and build every table of this geometry: lt_apply with up to n_baby baby steps then
+        allocates nothing and copies nothing to the device."""
+        check(lib.mfhe_lt_reserve(self._h, npoly, level, key_level, alpha, special_start, nspecial, n_baby),
+              "lt_reserve")
+
+    def lt_apply(self, c0, c1, pt, out0, out1, npoly, level, key_level, alpha, special_start, nspecial, baby_elt,
+                 giant_elt, gk_baby, gk_giant, term_giant, term_baby, pt_level=None, in_stride=None, pt_stride=None,
+                 out_stride=None, stream=None):
+        """(out0, out1) = the linear transform of the ciphertext (c0, c1), each [npoly][level][N], by the plaintexts pt
+        [nterms][pt_level + K][N]: term t multiplies plaintext t by baby step term_baby[t] inside giant step
+        term_giant[t] (non-decreasing).  baby_elt, giant_elt: Galois elements, entry 0 is 1; gk_baby, gk_giant: lists
+        of Galois keys (device tensors, entry 0 and unused steps may be None).  bsgs_plan gives the lists."""
+        pt_level = level if pt_level is None else pt_level
+        ist = level * self.N if in_stride is None else in_stride
+        ost = level * self.N if out_stride is None else out_stride
+        tst = (pt_level + nspecial) * self.N if pt_stride is None else pt_stride
+        nb, ng, nt = len(baby_elt), len(giant_elt), len(term_giant)
+        if len(gk_baby) != nb or len(gk_giant) != ng or len(term_baby) != nt:
+            raise ValueError("lt_apply: list lengths differ")
+        for t, what in ((c0, "c0"), (c1, "c1")):
+            self._need_polys(t, npoly, ist, level, self.N, f"lt_apply {what}")
+        for t, what in ((out0, "out0"), (out1, "out1")):
+            self._need_polys(t, npoly, ost, level, self.N, f"lt_apply {what}")
+        self._need_polys(pt, nt, tst, pt_level + nspecial, self.N, "lt_apply pt")
+        kbeta, kw = -(-key_level // max(alpha, 1)), 2 * (key_level + nspecial) * self.N
+        for k in list(gk_baby) + list(gk_giant):
+            if k is not None:
+                self._need_polys(k, kbeta, kw, 2 * (key_level + nspecial), self.N, "lt_apply key")
+        # the ctypes arrays stay referenced by these locals across the call
+        a_be, a_ge = (_int * max(nb, 1))(*baby_elt), (_int * max(ng, 1))(*giant_elt)
+        a_kb = (_vp * max(nb, 1))(*[_ptr(k) for k in gk_baby])
+        a_kg = (_vp * max(ng, 1))(*[_ptr(k) for k in gk_giant])
+        a_tg, a_tb = (_int * max(nt, 1))(*term_giant), (_int * max(nt, 1))(*term_baby)
+        plan = LtPlan(nb, ng, nt, a_be, a_ge, a_kb, a_kg, a_tg, a_tb)
+        check(lib.mfhe_lt_apply(self._h, ctypes.byref(plan), _ptr(c0), _ptr(c1), ist, _ptr(pt), tst, pt_level,
+                                _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha, special_start, nspecial,
+                                _stream_ptr(stream)), "lt_apply")
+        return out0, out1
+
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
         """RCCL exchange of this rank's [npoly][L/G][ncoeff] residue shard + compose of its polynomial slice
         (include/mfhe.h mfhe_crt_recombine_sharded); out: npoly/G * ncoeff f64."""
@@ -887,6 +996,34 @@ def galois_elt(step: int, log_n: int) -> int:
 def galois_conj(log_n: int) -> int:
     """The Galois element of the conjugation: 2N - 1."""
     return (2 << log_n) - 1
+
+
+def bsgs_plan(steps, n1: int, log_n: int) -> dict:
+    """Split the slot rotations `steps` (the diagonals of a matrix; taken mod N/2, duplicates dropped) for a
+    baby-step giant-step transform with n1 baby steps: k = a n1 + b, 0 <= b < n1.  Returns the lists Context.lt_apply
+    takes and what the caller needs to lay out plaintexts and keys:
+      baby_steps / giant_steps   rotations of the steps in use, ascending, entry 0 is 0 (giant steps are multiples of n1)
+      baby_elt / giant_elt       their Galois elements (galois_elt), entry 0 is 1
+      term_step                  the rotation k of term t, sorted by (giant, baby): plaintext t holds diagonal k,
+                                 pre-rotated by -giant_steps[term_giant[t]]
+      term_giant / term_baby     indices into giant_steps / baby_steps
+      key_steps                  the rotations a Galois key is needed for: every step in use but 0"""
+    if n1 < 1:
+        raise ValueError("bsgs_plan: n1 < 1")
+    nslots = 1 << (log_n - 1)
+    ks = sorted({int(k) % nslots for k in steps})
+    baby_steps = sorted({0} | {k % n1 for k in ks})
+    giant_steps = sorted({0} | {k - k % n1 for k in ks})
+    return {
+        "baby_steps": baby_steps,
+        "giant_steps": giant_steps,
+        "baby_elt": [galois_elt(b, log_n) for b in baby_steps],
+        "giant_elt": [galois_elt(g, log_n) for g in giant_steps],
+        "term_step": ks,
+        "term_giant": [giant_steps.index(k - k % n1) for k in ks],
+        "term_baby": [baby_steps.index(k % n1) for k in ks],
+        "key_steps": sorted({s for s in baby_steps + giant_steps if s}),
+    }
 
 
 def to_device_u64(arr, device="cuda"):
