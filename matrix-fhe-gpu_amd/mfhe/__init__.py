@@ -29,6 +29,7 @@ OPT_CGEMM_MFMA, OPT_HE_FUSED, OPT_TRACE_SPLIT = 10, 11, 12
 XCHG_ALLGATHER, XCHG_ALLTOALL = 0, 1
 BCONV_FAST, BCONV_CENTERED = 0, 1
 KS_ADD = 1                      # keyswitch: add the results to what out0 / out1 hold (relinearisation)
+CTMUL_RESCALE = 1               # ctmul: after relinearising, ModDown both outputs by limb level - 1
 RECOMBINE_ROWS_GLOBAL = 1
 RECOMBINE_EXCHANGE_ONLY = 2     # measurement: exchanges only, composes skipped (out untouched)
 RECOMBINE_AFTER_PREV = 4        # the shard was complete when the previous chunked call on the comm was entered
@@ -153,6 +154,11 @@ _sig("mfhe_lt_pt_mac",
 _sig("mfhe_lt_reserve", [_vp, _sz, _int, _int, _int, _int, _int, _int])
 _sig("mfhe_lt_apply", [_vp, ctypes.POINTER(LtPlan), _vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _sz, _sz, _int, _int, _int,
                        _int, _int, _vp])
+CTMUL_MAX_TERMS = 64            # ctmul_tensor / ctmul: most terms of one sum
+_sig("mfhe_ctmul_tensor", [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _vp, _vp, _sz, _vp, _sz, _sz, _int, _vp])
+_sig("mfhe_ctmul_reserve", [_vp, _sz, _int, _int, _int, _int, _int, _int])
+_sig("mfhe_ctmul_apply", [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _vp, _vp, _vp, _sz, _sz, _int, _int, _int,
+                          _int, _int, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -802,6 +808,70 @@ class Context:
         check(lib.mfhe_lt_apply(self._h, ctypes.byref(plan), _ptr(c0), _ptr(c1), ist, _ptr(pt), tst, pt_level,
                                 _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha, special_start, nspecial,
                                 _stream_ptr(stream)), "lt_apply")
+        return out0, out1
+
+    # ---- ciphertext products (include/mfhe.h): the geometry of the key switch; a ciphertext is a pair of
+    # [level][N] polynomials, a product a sum over nterms pairs of ciphertexts relinearised once
+    def _ctmul_operands(self, a0, a1, b0, b1, nterms, npoly, level, a_term_stride, a_poly_stride, b_term_stride,
+                        b_poly_stride, what):
+        """Dense strides by default, the operand buffers size-checked: (a_term, a_poly, b_term, b_poly)."""
+        if (b0 is None) != (b1 is None):
+            raise ValueError(f"{what}: b0 and b1 are both given or both None (the square form)")
+        lw = level * self.N
+        apst = lw if a_poly_stride is None else a_poly_stride
+        atst = npoly * apst if a_term_stride is None else a_term_stride
+        bpst = lw if b_poly_stride is None else b_poly_stride
+        btst = npoly * bpst if b_term_stride is None else b_term_stride
+        ops = [(a0, "a0", atst, apst), (a1, "a1", atst, apst)]
+        if b0 is not None:
+            ops += [(b0, "b0", btst, bpst), (b1, "b1", btst, bpst)]
+        for t, name, tst, pst in ops:
+            self._need_polys(t, npoly, pst, level, self.N, f"{what} {name} (one term)")
+            _need(t, (nterms - 1) * tst + (npoly - 1) * pst + lw if npoly and nterms > 0 else 0, f"{what} {name}")
+        return atst, apst, btst, bpst
+
+    def ctmul_tensor(self, a0, a1, b0, b1, d0, d1, d2, npoly, level, nterms=1, a_term_stride=None,
+                     a_poly_stride=None, b_term_stride=None, b_poly_stride=None, d01_stride=None, d2_stride=None,
+                     stream=None):
+        """(d0, d1, d2), each [npoly][level][N] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1)[t] mod q_r for the ciphertexts
+        (a0, a1) and (b0, b1), each pointer [nterms][npoly][level][N] with a term stride and a poly stride.
+        b0 = b1 = None is the square form: (sum a0^2, 2 sum a0 a1, sum a1^2).  One launch."""
+        atst, apst, btst, bpst = self._ctmul_operands(a0, a1, b0, b1, nterms, npoly, level, a_term_stride,
+                                                      a_poly_stride, b_term_stride, b_poly_stride, "ctmul_tensor")
+        ost = level * self.N if d01_stride is None else d01_stride
+        o2st = level * self.N if d2_stride is None else d2_stride
+        self._need_polys(d0, npoly, ost, level, self.N, "ctmul_tensor d0")
+        self._need_polys(d1, npoly, ost, level, self.N, "ctmul_tensor d1")
+        self._need_polys(d2, npoly, o2st, level, self.N, "ctmul_tensor d2")
+        check(lib.mfhe_ctmul_tensor(self._h, _ptr(a0), _ptr(a1), atst, apst, _ptr(b0), _ptr(b1), btst, bpst, nterms,
+                                    _ptr(d0), _ptr(d1), ost, _ptr(d2), o2st, npoly, level, _stream_ptr(stream)),
+              "ctmul_tensor")
+        return d0, d1, d2
+
+    def ctmul_reserve(self, npoly, level, key_level, alpha, special_start, nspecial, flags=0):
+        """Grow the workspace and build every table of this geometry (the rescale's with CTMUL_RESCALE): ctmul then
+        allocates nothing and copies nothing to the device."""
+        check(lib.mfhe_ctmul_reserve(self._h, npoly, level, key_level, alpha, special_start, nspecial, flags),
+              "ctmul_reserve")
+
+    def ctmul(self, a0, a1, b0, b1, rlk, out0, out1, npoly, level, key_level, alpha, special_start, nspecial,
+              nterms=1, flags=0, a_term_stride=None, a_poly_stride=None, b_term_stride=None, b_poly_stride=None,
+              out_stride=None, stream=None):
+        """(out0, out1), each [npoly][level][N] = the relinearised sum of the nterms products of the ciphertexts
+        (a0, a1) and (b0, b1) (b0 = b1 = None: the squares of (a0, a1)) with the relinearisation key rlk:
+        ctmul_tensor, then keyswitch(KS_ADD) of d2.  flags: CTMUL_RESCALE also divides by q_(level-1); rows
+        [0, level - 1) of the outputs then hold the result at level - 1."""
+        atst, apst, btst, bpst = self._ctmul_operands(a0, a1, b0, b1, nterms, npoly, level, a_term_stride,
+                                                      a_poly_stride, b_term_stride, b_poly_stride, "ctmul")
+        ost = level * self.N if out_stride is None else out_stride
+        self._need_polys(out0, npoly, ost, level, self.N, "ctmul out0")
+        self._need_polys(out1, npoly, ost, level, self.N, "ctmul out1")
+        if rlk is not None:
+            self._need_polys(rlk, -(-key_level // max(alpha, 1)), 2 * (key_level + nspecial) * self.N,
+                             2 * (key_level + nspecial), self.N, "ctmul rlk")
+        check(lib.mfhe_ctmul_apply(self._h, _ptr(a0), _ptr(a1), atst, apst, _ptr(b0), _ptr(b1), btst, bpst, nterms,
+                                   _ptr(rlk), _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha,
+                                   special_start, nspecial, flags, _stream_ptr(stream)), "ctmul")
         return out0, out1
 
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
