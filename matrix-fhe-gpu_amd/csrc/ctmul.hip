@@ -30,29 +30,6 @@ namespace mfhe {
 
 // largest term count whose operands stay in registers (DESIGN.md §3.12 has the resource table behind it)
 constexpr int kCtmulUnroll = 6;
-// terms between two reductions of the running sums
-constexpr int kCtmulFold = 8;
-
-// one term into the three sums: four products, or three in the square form (s1 then holds sum a0 a1, doubled at the
-// reduction)
-template <int V, bool SQ>
-static __device__ __forceinline__ void ct_term(const uint64_t (&x0)[V], const uint64_t (&x1)[V],
-                                               const uint64_t (&y0)[V], const uint64_t (&y1)[V], u128 (&s0)[V],
-                                               u128 (&s1)[V], u128 (&s2)[V]) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-        if (SQ) {
-            s0[k] += (u128)x0[k] * x0[k];
-            s1[k] += (u128)x0[k] * x1[k];
-            s2[k] += (u128)x1[k] * x1[k];
-        } else {
-            s0[k] += (u128)x0[k] * y0[k];
-            s1[k] += (u128)x0[k] * y1[k];
-            s1[k] += (u128)x1[k] * y0[k];
-            s2[k] += (u128)x1[k] * y1[k];
-        }
-    }
-}
 
 // NT: terms (template-unrolled, every operand in registers) or 0 (chunked loop over a.nterms); V: coefficients per
 // thread; SQ: the square form, b0 and b1 unread.  dmod is indexed by the block's row: scalar loads.
@@ -192,12 +169,6 @@ struct CtmulOperands {
     int nterms;
 };
 
-// A range of device words, for the overlap checks.
-struct CtmulRange {
-    const uint64_t* p;
-    size_t words;
-};
-
 // Pointers, term count and strides of the operands (lw = level * N); in[0 .. *nin) = the ranges they span.
 static int ctmul_check_operands(const std::string& w, const CtmulOperands& o, size_t npoly, size_t lw, CtmulRange in[4],
                                 int* nin) {
@@ -220,7 +191,7 @@ static int ctmul_check_operands(const std::string& w, const CtmulOperands& o, si
 }
 
 // no output may overlap an input or another output
-static int ctmul_check_overlap(const std::string& w, const CtmulRange* in, int nin, const CtmulRange* out, int nout) {
+int ctmul_check_overlap(const std::string& w, const CtmulRange* in, int nin, const CtmulRange* out, int nout) {
     for (int k = 0; k < nout; ++k) {
         for (int i = 0; i < nin; ++i)
             if (ks_ranges_overlap(in[i].p, in[i].words, out[k].p, out[k].words))
@@ -245,11 +216,11 @@ static CtmulArgs ctmul_args(const CtmulOperands& o, uint64_t* d0, uint64_t* d1, 
 
 // words of mfhe_ctmul_apply's block of the workspace: the key switch's block (the rescale's scratch, 2 npoly level N
 // words, reuses it), then d2 [npoly][level][N]
-static size_t ctmul_ws_words(size_t npoly, int beta, size_t rows, int level, size_t N) {
+size_t ctmul_ws_words(size_t npoly, int beta, size_t rows, int level, size_t N) {
     return ks_ws_words(npoly, beta, rows, N) + npoly * (size_t)level * N;
 }
 
-static int ctmul_check_flags(const char* what, int flags, int level) {
+int ctmul_check_flags(const char* what, int flags, int level) {
     const std::string w(what);
     if (flags & ~MFHE_CTMUL_RESCALE) return set_error(MFHE_EINVAL, w + ": unknown flag");
     if ((flags & MFHE_CTMUL_RESCALE) && level == 1)
@@ -257,11 +228,60 @@ static int ctmul_check_flags(const char* what, int flags, int level) {
     return MFHE_OK;
 }
 
+#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
+
+int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride,
+                        size_t npoly, const KsGeom& g, int alpha, const KsTables& t, const uint64_t* rs, int flags,
+                        hipStream_t st) {
+    const int level = g.level, special_start = g.special_start, nspecial = g.nspecial;
+    const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
+    const size_t pw = rows * N;                                   // one raised polynomial
+    uint64_t* raised = (uint64_t*)c->ws;                          // [beta][npoly][rows][N]   the key switch's block
+    uint64_t* acc = raised + (size_t)t.beta * npoly * pw;         // [npoly][2][rows][N]
+    uint64_t* scratch = acc + 2 * npoly * pw;                     // 2 npoly * rows * N words
+    uint64_t* d2 = (uint64_t*)c->ws + ks_ws_words(npoly, t.beta, rows, N);   // [npoly][level][N]
+    // the body of mfhe_keyswitch with MFHE_KS_ADD on d2
+    for (int j = 0; j < t.beta; ++j) {
+        const int ds = j * alpha, dc = level - ds < alpha ? level - ds : alpha;
+        RC(ntt_modup_body(c, d2, lw, raised + (size_t)j * npoly * pw, pw, npoly, ds, dc, t.plan[j],
+                          &t.tab[(size_t)3 * j], scratch, st));
+    }
+    KsipArgs a{};
+    a.raised = raised; a.ksk = d_rlk; a.acc = acc;
+    a.digit_stride = npoly * pw; a.poly_stride = pw; a.acc_stride = 2 * pw;
+    a.ncoeff = N; a.npoly = npoly; a.ndigits = t.beta; a.g = g;
+    RC(launch_ksk_inner_product(c, a, st));
+    const uint64_t* cen = nullptr;
+    RC(ntt_moddown_center(c, acc, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
+    uint64_t* outs[2] = {d_out0, d_out1};
+    for (int k = 0; k < 2; ++k)
+        RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_poly_stride,
+                            outs[k], npoly, level, nspecial, t.down, st));
+    if (!(flags & MFHE_CTMUL_RESCALE)) return MFHE_OK;
+    // The rescale: mfhe_ntt_moddown(keep = level - 1, drop = limb level - 1) in place on each output, its scratch the
+    // key switch's block.  The two outputs are one batch of 2 npoly polynomials when one follows the other at the
+    // poly stride (any two single polynomials do); the work per polynomial is the same either way.
+    const int keep = level - 1;
+    const size_t kw = (size_t)keep * N;
+    uint64_t* lo = d_out0 < d_out1 ? d_out0 : d_out1;
+    const size_t gap = (size_t)((d_out0 < d_out1 ? d_out1 : d_out0) - lo);
+    const size_t batch_stride = npoly == 1 ? gap : gap == npoly * out_poly_stride ? out_poly_stride : 0;
+    uint64_t* ws = (uint64_t*)c->ws;
+    if (batch_stride) {
+        RC(ntt_moddown_center(c, lo, batch_stride, 2 * npoly, keep, keep, 1, rs, ws, &cen, st));
+        return launch_sub_scale(c, lo, batch_stride, cen, kw, lo, batch_stride, nullptr, 2 * npoly, keep, 1, rs, st);
+    }
+    for (int k = 0; k < 2; ++k) {
+        RC(ntt_moddown_center(c, outs[k], out_poly_stride, npoly, keep, keep, 1, rs, ws, &cen, st));
+        RC(launch_sub_scale(c, outs[k], out_poly_stride, cen, kw, outs[k], out_poly_stride, nullptr, npoly, keep, 1,
+                            rs, st));
+    }
+    return MFHE_OK;
+}
+
 }  // namespace mfhe
 
 using namespace mfhe;
-
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 extern "C" int mfhe_ctmul_tensor(mfhe_ctx* c, const uint64_t* d_a0, const uint64_t* d_a1, size_t a_term_stride,
                                  size_t a_poly_stride, const uint64_t* d_b0, const uint64_t* d_b1, size_t b_term_stride,
@@ -332,48 +352,8 @@ extern "C" int mfhe_ctmul_apply(mfhe_ctx* c, const uint64_t* d_a0, const uint64_
     if (flags & MFHE_CTMUL_RESCALE) RC(bconv_table(c, level - 1, 1, 0, level - 1, &rs));
     RC(grow_ws(c, ctmul_ws_words(npoly, t.beta, rows, level, N) * 8));
     hipStream_t st = (hipStream_t)s;
-    const size_t pw = rows * N;                                   // one raised polynomial
-    uint64_t* raised = (uint64_t*)c->ws;                          // [beta][npoly][rows][N]   the key switch's block
-    uint64_t* acc = raised + (size_t)t.beta * npoly * pw;         // [npoly][2][rows][N]
-    uint64_t* scratch = acc + 2 * npoly * pw;                     // 2 npoly * rows * N words
     uint64_t* d2 = (uint64_t*)c->ws + ks_ws_words(npoly, t.beta, rows, N);   // [npoly][level][N]
 
     RC(launch_ctmul_tensor(c, ctmul_args(o, d_out0, d_out1, out_poly_stride, d2, lw, npoly, level, N), st));
-    // the body of mfhe_keyswitch with MFHE_KS_ADD on d2
-    for (int j = 0; j < t.beta; ++j) {
-        const int ds = j * alpha, dc = level - ds < alpha ? level - ds : alpha;
-        RC(ntt_modup_body(c, d2, lw, raised + (size_t)j * npoly * pw, pw, npoly, ds, dc, t.plan[j],
-                          &t.tab[(size_t)3 * j], scratch, st));
-    }
-    KsipArgs a{};
-    a.raised = raised; a.ksk = d_rlk; a.acc = acc;
-    a.digit_stride = npoly * pw; a.poly_stride = pw; a.acc_stride = 2 * pw;
-    a.ncoeff = N; a.npoly = npoly; a.ndigits = t.beta; a.g = g;
-    RC(launch_ksk_inner_product(c, a, st));
-    const uint64_t* cen = nullptr;
-    RC(ntt_moddown_center(c, acc, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
-    uint64_t* outs[2] = {d_out0, d_out1};
-    for (int k = 0; k < 2; ++k)
-        RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_poly_stride,
-                            outs[k], npoly, level, nspecial, t.down, st));
-    if (!(flags & MFHE_CTMUL_RESCALE)) return MFHE_OK;
-    // The rescale: mfhe_ntt_moddown(keep = level - 1, drop = limb level - 1) in place on each output, its scratch the
-    // key switch's block.  The two outputs are one batch of 2 npoly polynomials when one follows the other at the
-    // poly stride (any two single polynomials do); the work per polynomial is the same either way.
-    const int keep = level - 1;
-    const size_t kw = (size_t)keep * N;
-    uint64_t* lo = d_out0 < d_out1 ? d_out0 : d_out1;
-    const size_t gap = (size_t)((d_out0 < d_out1 ? d_out1 : d_out0) - lo);
-    const size_t batch_stride = npoly == 1 ? gap : gap == npoly * out_poly_stride ? out_poly_stride : 0;
-    uint64_t* ws = (uint64_t*)c->ws;
-    if (batch_stride) {
-        RC(ntt_moddown_center(c, lo, batch_stride, 2 * npoly, keep, keep, 1, rs, ws, &cen, st));
-        return launch_sub_scale(c, lo, batch_stride, cen, kw, lo, batch_stride, nullptr, 2 * npoly, keep, 1, rs, st);
-    }
-    for (int k = 0; k < 2; ++k) {
-        RC(ntt_moddown_center(c, outs[k], out_poly_stride, npoly, keep, keep, 1, rs, ws, &cen, st));
-        RC(launch_sub_scale(c, outs[k], out_poly_stride, cen, kw, outs[k], out_poly_stride, nullptr, npoly, keep, 1,
-                            rs, st));
-    }
-    return MFHE_OK;
+    return ctmul_relin_rescale(c, d_rlk, d_out0, d_out1, out_poly_stride, npoly, g, alpha, t, rs, flags, st);
 }

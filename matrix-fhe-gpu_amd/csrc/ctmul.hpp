@@ -1,12 +1,39 @@
 // ctmul.hpp -- ciphertext products on the key switch's layout (ctmul.hip): the kernel arguments and the launcher of
-// the summed tensor product.
+// the summed tensor product, and what the matrix product (ctmat.hip) shares with it: the term of the three sums, the
+// argument checks and the relinearise and rescale tail of the driver.
 #pragma once
+#include <string>
+
 #include "keyswitch.hpp"
+#include "mod128.hpp"
 
 namespace mfhe {
 
 // most terms of one tensor sum
 constexpr int kCtmulMaxTerms = 64;
+// terms between two reductions of the running sums
+constexpr int kCtmulFold = 8;
+
+// one term into the three sums: four products, or three in the square form (s1 then holds sum a0 a1, doubled at the
+// reduction)
+template <int V, bool SQ>
+static __device__ __forceinline__ void ct_term(const uint64_t (&x0)[V], const uint64_t (&x1)[V],
+                                               const uint64_t (&y0)[V], const uint64_t (&y1)[V], u128 (&s0)[V],
+                                               u128 (&s1)[V], u128 (&s2)[V]) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        if (SQ) {
+            s0[k] += (u128)x0[k] * x0[k];
+            s1[k] += (u128)x0[k] * x1[k];
+            s2[k] += (u128)x1[k] * x1[k];
+        } else {
+            s0[k] += (u128)x0[k] * y0[k];
+            s1[k] += (u128)x0[k] * y1[k];
+            s1[k] += (u128)x1[k] * y0[k];
+            s2[k] += (u128)x1[k] * y1[k];
+        }
+    }
+}
 
 // Kernel arguments of the summed tensor product.  Strides and ncoeff in units of V words (V = 1 scalar, V = 2 the
 // 16-byte form).  a0, a1 [nterms][npoly][level][ncoeff] with a term stride and a poly stride, b0, b1 the same with
@@ -26,5 +53,26 @@ struct CtmulArgs {
 // ncoeff given in words; the 16-byte form is chosen here when ncoeff and every stride are even and every buffer
 // 16-byte aligned.  Arguments already checked.
 int launch_ctmul_tensor(mfhe_ctx* c, CtmulArgs a, hipStream_t st);
+
+// ---- shared with ctmat.hip ----
+// A range of device words, for the overlap checks.
+struct CtmulRange {
+    const uint64_t* p;
+    size_t words;
+};
+// no output may overlap an input or another output
+int ctmul_check_overlap(const std::string& w, const CtmulRange* in, int nin, const CtmulRange* out, int nout);
+// the flags of a driver: unknown ones, and MFHE_CTMUL_RESCALE at level 1
+int ctmul_check_flags(const char* what, int flags, int level);
+// words of a driver's block of the workspace: the key switch's block (the rescale's scratch, 2 npoly level N words,
+// reuses it), then d2 [npoly][level][N]
+size_t ctmul_ws_words(size_t npoly, int beta, size_t rows, int level, size_t N);
+// The tail of a driver once the tensor sum has left d0, d1 in the outputs ([npoly][level][N] at out_poly_stride) and
+// d2 dense behind the key switch's block of the workspace: the body of mfhe_keyswitch with MFHE_KS_ADD on d2, then
+// with MFHE_CTMUL_RESCALE (rs: the table of limb level - 1 -> [0, level - 1)) the ModDown of both outputs in place.
+// Tables built and workspace grown by the caller.
+int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride,
+                        size_t npoly, const KsGeom& g, int alpha, const KsTables& t, const uint64_t* rs, int flags,
+                        hipStream_t st);
 
 }  // namespace mfhe

@@ -159,6 +159,12 @@ _sig("mfhe_ctmul_tensor", [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _v
 _sig("mfhe_ctmul_reserve", [_vp, _sz, _int, _int, _int, _int, _int, _int])
 _sig("mfhe_ctmul_apply", [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _vp, _vp, _vp, _sz, _sz, _int, _int, _int,
                           _int, _int, _int, _vp])
+CTMAT_TILE = (2, 2)             # ctmat_tensor: outputs one thread owns (csrc/ctmat.hip kCtmatTM x kCtmatTN)
+_sig("mfhe_ctmat_tensor", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _vp, _sz, _sz,
+                           _sz, _vp, _sz, _sz, _sz, _sz, _int, _vp])
+_sig("mfhe_ctmat_reserve", [_vp, _int, _int, _sz, _int, _int, _int, _int, _int, _int])
+_sig("mfhe_ctmat_apply", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _vp, _vp, _sz,
+                          _sz, _int, _int, _int, _int, _int, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -872,6 +878,69 @@ class Context:
         check(lib.mfhe_ctmul_apply(self._h, _ptr(a0), _ptr(a1), atst, apst, _ptr(b0), _ptr(b1), btst, bpst, nterms,
                                    _ptr(rlk), _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha,
                                    special_start, nspecial, flags, _stream_ptr(stream)), "ctmul")
+        return out0, out1
+
+    # ---- products of matrices of ciphertexts (include/mfhe.h): C = A B, A m x k and B k x n ciphertexts of npoly
+    # polynomials per component; one tiled launch where m n ctmul_tensor calls stream A n times and B m times
+    def _ctmat_need(self, t, rows, cols, npoly, level, row, col, poly, what):
+        """The buffer holds a rows x cols matrix of entries at these strides."""
+        lw = level * self.N
+        last = (rows - 1) * row + (cols - 1) * col + (npoly - 1) * poly + lw
+        _need(t, last if npoly and rows > 0 and cols > 0 else 0, what)
+
+    def _ctmat_operands(self, a0, a1, b0, b1, m, n, k, npoly, level, a_strides, b_strides, what):
+        """Dense strides [m][k][npoly][level][N] and [k][n][npoly][level][N] by default, the operand buffers
+        size-checked: ((a_row, a_col, a_poly), (b_row, b_col, b_poly))."""
+        lw = level * self.N
+        a = (k * npoly * lw, npoly * lw, lw) if a_strides is None else tuple(a_strides)
+        b = (n * npoly * lw, npoly * lw, lw) if b_strides is None else tuple(b_strides)
+        for t, name in ((a0, "a0"), (a1, "a1")):
+            self._ctmat_need(t, m, k, npoly, level, *a, f"{what} {name}")
+        for t, name in ((b0, "b0"), (b1, "b1")):
+            self._ctmat_need(t, k, n, npoly, level, *b, f"{what} {name}")
+        return a, b
+
+    def ctmat_tensor(self, a0, a1, b0, b1, d0, d1, d2, m, n, k, npoly, level, a_strides=None, b_strides=None,
+                     d01_strides=None, d2_strides=None, stream=None):
+        """(d0, d1, d2)[i][j] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1) of a[i][t] and b[t][j] mod q_r for the m x k matrix
+        (a0, a1) and the k x n matrix (b0, b1) of ciphertexts, npoly polynomials [level][N] per entry and component.  Every
+        *_strides is (row, col, poly) in words, dense by default: [m][k], [k][n] and [m][n] entries of
+        [npoly][level][N]; a transposed operand is the same memory with row and col swapped.  One launch, bit-identical
+        to m n ctmul_tensor calls."""
+        a, b = self._ctmat_operands(a0, a1, b0, b1, m, n, k, npoly, level, a_strides, b_strides, "ctmat_tensor")
+        lw = level * self.N
+        o = (n * npoly * lw, npoly * lw, lw) if d01_strides is None else tuple(d01_strides)
+        o2 = (n * npoly * lw, npoly * lw, lw) if d2_strides is None else tuple(d2_strides)
+        self._ctmat_need(d0, m, n, npoly, level, *o, "ctmat_tensor d0")
+        self._ctmat_need(d1, m, n, npoly, level, *o, "ctmat_tensor d1")
+        self._ctmat_need(d2, m, n, npoly, level, *o2, "ctmat_tensor d2")
+        check(lib.mfhe_ctmat_tensor(self._h, _ptr(a0), _ptr(a1), *a, _ptr(b0), _ptr(b1), *b, m, n, k, _ptr(d0),
+                                    _ptr(d1), *o, _ptr(d2), *o2, npoly, level, _stream_ptr(stream)), "ctmat_tensor")
+        return d0, d1, d2
+
+    def ctmat_reserve(self, m, n, npoly, level, key_level, alpha, special_start, nspecial, flags=0):
+        """Grow the workspace and build every table of this geometry (the rescale's with CTMUL_RESCALE): ctmat then
+        allocates nothing and copies nothing to the device."""
+        check(lib.mfhe_ctmat_reserve(self._h, m, n, npoly, level, key_level, alpha, special_start, nspecial, flags),
+              "ctmat_reserve")
+
+    def ctmat(self, a0, a1, b0, b1, rlk, out0, out1, m, n, k, npoly, level, key_level, alpha, special_start, nspecial,
+              flags=0, a_strides=None, b_strides=None, out_stride=None, stream=None):
+        """(out0, out1), each [m][n][npoly][level][N] at one poly stride = the relinearised product of the m x k matrix
+        (a0, a1) and the k x n matrix (b0, b1) of ciphertexts with the relinearisation key rlk: ctmat_tensor, then one
+        keyswitch(KS_ADD) of d2 over all m n npoly polynomials.  flags: CTMUL_RESCALE also divides by q_(level-1).
+        Bit-identical to m n ctmul calls, one per entry."""
+        a, b = self._ctmat_operands(a0, a1, b0, b1, m, n, k, npoly, level, a_strides, b_strides, "ctmat")
+        ost = level * self.N if out_stride is None else out_stride
+        batch = max(m, 0) * max(n, 0) * npoly
+        self._need_polys(out0, batch, ost, level, self.N, "ctmat out0")
+        self._need_polys(out1, batch, ost, level, self.N, "ctmat out1")
+        if rlk is not None:
+            self._need_polys(rlk, -(-key_level // max(alpha, 1)), 2 * (key_level + nspecial) * self.N,
+                             2 * (key_level + nspecial), self.N, "ctmat rlk")
+        check(lib.mfhe_ctmat_apply(self._h, _ptr(a0), _ptr(a1), *a, _ptr(b0), _ptr(b1), *b, m, n, k, _ptr(rlk),
+                                   _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha, special_start,
+                                   nspecial, flags, _stream_ptr(stream)), "ctmat")
         return out0, out1
 
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
