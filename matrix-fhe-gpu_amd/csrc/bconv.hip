@@ -273,8 +273,8 @@ int launch_bconv(BconvArgs a, size_t npoly, int kernel_mode, hipStream_t st) {
     return MFHE_OK;
 }
 
-static int launch_copy_rows(const uint64_t* src, size_t src_stride, uint64_t* dst, size_t dst_stride, size_t npoly,
-                            size_t words, hipStream_t st) {
+int launch_copy_rows(const uint64_t* src, size_t src_stride, uint64_t* dst, size_t dst_stride, size_t npoly,
+                     size_t words, hipStream_t st) {
     const uint64_t total = (uint64_t)npoly * words;
     const uint64_t blocks = (total + 255) / 256;
     if (blocks == 0) return MFHE_OK;

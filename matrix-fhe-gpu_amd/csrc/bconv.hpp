@@ -40,7 +40,10 @@ int bconv_table(mfhe_ctx* c, int src_start, int src_count, int dst_start, int ds
 // ncoeff and both strides are even and both buffers 16-byte aligned).  kernel_mode: kBconv*.
 int launch_bconv(BconvArgs a, size_t npoly, int kernel_mode, hipStream_t st);
 
-// ---- shared with keyswitch.hip ----
+// ---- shared with keyswitch.hip and slot.hip ----
+// One launch: dst[p][w] = src[p][w] for w < words, the npoly blocks src_stride / dst_stride words apart.
+int launch_copy_rows(const uint64_t* src, size_t src_stride, uint64_t* dst, size_t dst_stride, size_t npoly,
+                     size_t words, hipStream_t st);
 // Grow the context workspace to `need` bytes (frees and reallocates; nothing when it is large enough).
 int grow_ws(mfhe_ctx* c, size_t need);
 

@@ -198,6 +198,9 @@ struct mfhe_ctx {
         uint64_t* d_pmod;
     };
     std::vector<KskEntry> ksk_tabs;
+    // slot encoder (slot.hip): [N / 2] j with (5^j mod 2N - 1) / 4 == t; built on first use, owned by allocs, guarded by
+    // bconv_mu
+    uint32_t* d_slot_jinv = nullptr;
 
     std::vector<void*> allocs;  // everything above, freed at destroy
 };

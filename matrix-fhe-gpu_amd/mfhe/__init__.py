@@ -30,6 +30,8 @@ XCHG_ALLGATHER, XCHG_ALLTOALL = 0, 1
 BCONV_FAST, BCONV_CENTERED = 0, 1
 KS_ADD = 1                      # keyswitch: add the results to what out0 / out1 hold (relinearisation)
 CTMUL_RESCALE = 1               # ctmul: after relinearising, ModDown both outputs by limb level - 1
+SLOT_REAL = 1                   # slot_encode / slot_decode: real slots, N / 2 doubles per polynomial
+SLOT_COEFF = 2                  # slot_encode / slot_decode: residues in the coefficient domain (no NTT)
 RECOMBINE_ROWS_GLOBAL = 1
 RECOMBINE_EXCHANGE_ONLY = 2     # measurement: exchanges only, composes skipped (out untouched)
 RECOMBINE_AFTER_PREV = 4        # the shard was complete when the previous chunked call on the comm was entered
@@ -165,6 +167,10 @@ _sig("mfhe_ctmat_tensor", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz
 _sig("mfhe_ctmat_reserve", [_vp, _int, _int, _sz, _int, _int, _int, _int, _int, _int])
 _sig("mfhe_ctmat_apply", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _vp, _vp, _sz,
                           _sz, _int, _int, _int, _int, _int, _int, _vp])
+_dbl = ctypes.c_double
+_sig("mfhe_slot_reserve", [_vp, _sz, _int, _int, _int])
+_sig("mfhe_slot_encode", [_vp, _vp, _sz, _dbl, _vp, _sz, _sz, _int, _int, _int, _int, _vp])
+_sig("mfhe_slot_decode", [_vp, _vp, _sz, _dbl, _vp, _sz, _sz, _int, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -942,6 +948,50 @@ class Context:
                                    _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha, special_start,
                                    nspecial, flags, _stream_ptr(stream)), "ctmat")
         return out0, out1
+
+    # ---- CKKS slots (include/mfhe.h mfhe_slot_*): slot j of a polynomial m is m(zeta^(5^j)), zeta = e^(i pi / N) ----
+    def _slot_words(self, t, npoly, stride, flags, what):
+        """Checks a slot tensor (float64, interleaved (re, im) unless SLOT_REAL, or complex128) and returns the stride
+        in doubles: npoly blocks of N (N / 2 with SLOT_REAL) doubles."""
+        import torch
+        if t.dtype == torch.complex128:
+            if flags & SLOT_REAL:
+                raise ValueError(f"{what}: SLOT_REAL takes a float64 tensor")
+        elif t.dtype != torch.float64:
+            raise ValueError(f"{what}: slots are float64 or complex128, not {t.dtype}")
+        width = self.N // 2 if flags & SLOT_REAL else self.N
+        st = width if stride is None else stride
+        self._need_polys(t, npoly, st, 1, width, what)
+        return st
+
+    def slot_reserve(self, npoly, level, special_start=0, nspecial=0):
+        """Grow the workspace and build the table of this geometry: slot_encode and slot_decode of up to npoly
+        polynomials then allocate nothing and copy nothing to the device."""
+        check(lib.mfhe_slot_reserve(self._h, npoly, level, special_start, nspecial), "slot_reserve")
+
+    def slot_encode(self, slots, out, npoly, level, scale, special_start=0, nspecial=0, flags=0, slot_stride=None,
+                    out_stride=None, stream=None):
+        """out [npoly][level + nspecial][N] = the residues of rint(scale c), c the real polynomial whose slots are
+        `slots` ([npoly][N / 2] complex128, the same as [npoly][N] float64 interleaved; [npoly][N / 2] float64 with
+        SLOT_REAL), in the evaluation domain unless SLOT_COEFF.  Row r >= level is special limb special_start + r -
+        level.  slot_stride in doubles, out_stride in words."""
+        sst = self._slot_words(slots, npoly, slot_stride, flags, "slot_encode slots")
+        rows = level + nspecial
+        ost = rows * self.N if out_stride is None else out_stride
+        self._need_polys(out, npoly, ost, rows, self.N, "slot_encode out")
+        check(lib.mfhe_slot_encode(self._h, _ptr(slots), sst, float(scale), _ptr(out), ost, npoly, level,
+                                   special_start, nspecial, flags, _stream_ptr(stream)), "slot_encode")
+        return out
+
+    def slot_decode(self, src, slots, npoly, level, scale, flags=0, in_stride=None, slot_stride=None, stream=None):
+        """slots = the slot values of the polynomials src [npoly][level][N] (limbs [0, min(level, 2)) are read,
+        composed, centred and converted to f64), divided by scale.  Evaluation domain unless SLOT_COEFF."""
+        sst = self._slot_words(slots, npoly, slot_stride, flags, "slot_decode slots")
+        ist = level * self.N if in_stride is None else in_stride
+        self._need_polys(src, npoly, ist, min(level, 2), self.N, "slot_decode src")
+        check(lib.mfhe_slot_decode(self._h, _ptr(src), ist, float(scale), _ptr(slots), sst, npoly, level, flags,
+                                   _stream_ptr(stream)), "slot_decode")
+        return slots
 
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
         """RCCL exchange of this rank's [npoly][L/G][ncoeff] residue shard + compose of its polynomial slice
