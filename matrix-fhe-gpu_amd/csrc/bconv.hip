@@ -253,13 +253,7 @@ static BconvKernel pick_mode(int ns, int mode) {
 }
 
 int launch_bconv(BconvArgs a, size_t npoly, int kernel_mode, hipStream_t st) {
-    const bool wide = a.ncoeff % 2 == 0 && a.in_stride % 2 == 0 && a.out_stride % 2 == 0 &&
-                      (((uintptr_t)a.in | (uintptr_t)a.out) & 15) == 0;
-    if (wide) {
-        a.ncoeff /= 2;
-        a.in_stride /= 2;
-        a.out_stride /= 2;
-    }
+    const bool wide = ks_wide({&a.ncoeff, &a.in_stride, &a.out_stride}, {a.in, a.out});
     a.total = (uint64_t)npoly * a.ncoeff;
     a.lg = (a.ncoeff && !(a.ncoeff & (a.ncoeff - 1))) ? __builtin_ctzll(a.ncoeff) : -1;
     const uint64_t blocks = (a.total + 255) / 256;
@@ -420,8 +414,6 @@ int launch_sub_scale(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const 
 }  // namespace mfhe
 
 using namespace mfhe;
-
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 extern "C" int mfhe_rns_bconv_reserve(mfhe_ctx* c, int src_start, int src_count, int dst_start, int dst_count) {
     if (!c) return set_error(MFHE_EINVAL, "null ctx");

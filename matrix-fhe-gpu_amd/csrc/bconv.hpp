@@ -1,5 +1,6 @@
 // bconv.hpp -- launchers of the RNS basis conversion kernels (bconv.hip).
 #pragma once
+#include "ks_host.hpp"
 #include "mfhe_ctx.hpp"
 
 namespace mfhe {

@@ -185,28 +185,22 @@ __global__ __launch_bounds__(256, MFHE_CTMAT_WAVES) void ctmat_tensor_kernel(Ctm
 
 int launch_ctmat_tensor(mfhe_ctx* c, CtmatArgs a, hipStream_t st) {
     if (a.npoly == 0 || a.ncoeff == 0) return MFHE_OK;
-    const uint64_t odd = a.ncoeff | a.a_row | a.a_col | a.a_poly | a.b_row | a.b_col | a.b_poly | a.d01_row |
-                         a.d01_col | a.d01_poly | a.d2_row | a.d2_col | a.d2_poly;
-    const uintptr_t ptrs = (uintptr_t)a.a0 | (uintptr_t)a.a1 | (uintptr_t)a.b0 | (uintptr_t)a.b1 | (uintptr_t)a.d0 |
-                           (uintptr_t)a.d1 | (uintptr_t)a.d2;
-    const bool wide = MFHE_CTMAT_WIDE && odd % 2 == 0 && (ptrs & 15) == 0;
-    if (wide)
-        for (uint64_t* s : {&a.ncoeff, &a.a_row, &a.a_col, &a.a_poly, &a.b_row, &a.b_col, &a.b_poly, &a.d01_row,
-                            &a.d01_col, &a.d01_poly, &a.d2_row, &a.d2_col, &a.d2_poly})
-            *s /= 2;
+    const bool wide = MFHE_CTMAT_WIDE &&
+                      ks_wide({&a.ncoeff, &a.a_row, &a.a_col, &a.a_poly, &a.b_row, &a.b_col, &a.b_poly, &a.d01_row,
+                               &a.d01_col, &a.d01_poly, &a.d2_row, &a.d2_col, &a.d2_poly},
+                              {a.a0, a.a1, a.b0, a.b1, a.d0, a.d1, a.d2});
     const uint64_t tiles = (((uint64_t)a.m + kCtmatTM - 1) / kCtmatTM) * (((uint64_t)a.n + kCtmatTN - 1) / kCtmatTN);
     a.nwork = tiles * a.npoly;
-    const uint32_t block = a.ncoeff >= 256 ? 256 : (uint32_t)((a.ncoeff + 63) / 64 * 64);
-    const uint64_t bx = (a.ncoeff + block - 1) / block;
-    if (bx > 0x7fffffffull || a.level > 65535 || a.ncoeff > (1ull << 28) || a.nwork / tiles != a.npoly ||
+    const KsRowGrid rg = ks_row_grid(a.ncoeff);
+    if (rg.bx > 0x7fffffffull || a.level > 65535 || a.ncoeff > (1ull << 28) || a.nwork / tiles != a.npoly ||
         a.nwork > 0xffffffffull)
         return set_error(MFHE_EINVAL, "ctmat_tensor: too large for one launch");
-    const dim3 grid((uint32_t)bx, (uint32_t)a.level, (uint32_t)(a.nwork < 65535 ? a.nwork : 65535));
+    const dim3 grid((uint32_t)rg.bx, (uint32_t)a.level, (uint32_t)(a.nwork < 65535 ? a.nwork : 65535));
     if (wide)
-        hipLaunchKernelGGL((ctmat_tensor_kernel<2, kCtmatTM, kCtmatTN>), grid, dim3(block), 0, st, a,
+        hipLaunchKernelGGL((ctmat_tensor_kernel<2, kCtmatTM, kCtmatTN>), grid, dim3(rg.block), 0, st, a,
                            (const uint64_t*)c->d_dmod);
     else
-        hipLaunchKernelGGL((ctmat_tensor_kernel<1, kCtmatTM, kCtmatTN>), grid, dim3(block), 0, st, a,
+        hipLaunchKernelGGL((ctmat_tensor_kernel<1, kCtmatTM, kCtmatTN>), grid, dim3(rg.block), 0, st, a,
                            (const uint64_t*)c->d_dmod);
     MFHE_CHECK_LAUNCH("ctmat_tensor_kernel");
     return MFHE_OK;
@@ -246,7 +240,7 @@ struct CtmatOperands {
 
 // Pointers, shape and strides of the operands (lw = level * N); in[0 .. 4) = the ranges they span.
 static int ctmat_check_operands(const std::string& w, const CtmatOperands& o, size_t npoly, size_t lw,
-                                CtmulRange in[4]) {
+                                KsRange in[4]) {
     if (!o.a0 || !o.a1 || !o.b0 || !o.b1) return set_error(MFHE_EINVAL, w + ": null pointer");
     if (o.m < 1 || o.n < 1) return set_error(MFHE_EINVAL, w + ": m or n < 1");
     if (o.k < 1 || o.k > kCtmulMaxTerms) return set_error(MFHE_EINVAL, w + ": k outside [1, 64]");
@@ -287,8 +281,6 @@ static bool ctmat_batch(int m, int n, size_t npoly, size_t* batch) {
 
 using namespace mfhe;
 
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 extern "C" int mfhe_ctmat_tensor(mfhe_ctx* c, const uint64_t* d_a0, const uint64_t* d_a1, size_t a_row_stride,
                                  size_t a_col_stride, size_t a_poly_stride, const uint64_t* d_b0, const uint64_t* d_b1,
                                  size_t b_row_stride, size_t b_col_stride, size_t b_poly_stride, int m, int n, int k,
@@ -301,7 +293,7 @@ extern "C" int mfhe_ctmat_tensor(mfhe_ctx* c, const uint64_t* d_a0, const uint64
     const size_t N = c->N, lw = (size_t)level * N;
     const CtmatOperands o{d_a0, d_a1, a_row_stride, a_col_stride, a_poly_stride, d_b0, d_b1, b_row_stride,
                           b_col_stride, b_poly_stride, m, n, k};
-    CtmulRange in[4];
+    KsRange in[4];
     RC(ctmat_check_operands("ctmat_tensor", o, npoly, lw, in));
     if (d01_poly_stride < lw || d2_poly_stride < lw)
         return set_error(MFHE_EINVAL, "ctmat_tensor: output poly stride smaller than level * N");
@@ -310,29 +302,24 @@ extern "C" int mfhe_ctmat_tensor(mfhe_ctx* c, const uint64_t* d_a0, const uint64
     size_t osp = 0, o2sp = 0;
     if (!ctmat_span(d01, npoly, lw, &osp) || !ctmat_span(d2s, npoly, lw, &o2sp))
         return set_error(MFHE_EINVAL, "ctmat_tensor: entries of an output overlap at these strides");
-    const CtmulRange out[3] = {{d_d0, osp}, {d_d1, osp}, {d_d2, o2sp}};
-    RC(ctmul_check_overlap("ctmat_tensor", in, 4, out, 3));
+    const KsRange out[3] = {{d_d0, osp}, {d_d1, osp}, {d_d2, o2sp}};
+    RC(ks_check_overlap("ctmat_tensor", in, 4, out, 3));
     if (npoly == 0) return MFHE_OK;
     return launch_ctmat_tensor(c, ctmat_args(o, d_d0, d_d1, d01, d_d2, d2s, npoly, level, N), (hipStream_t)s);
 }
+
 
 extern "C" int mfhe_ctmat_reserve(mfhe_ctx* c, int m, int n, size_t npoly, int level, int key_level, int alpha,
                                   int special_start, int nspecial, int flags) {
     RC(ks_check_ctx(c));
     if (m < 1 || n < 1) return set_error(MFHE_EINVAL, "ctmat_reserve: m or n < 1");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "ctmat_reserve: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "ctmat_reserve"));
+    RC(ks_check_digits(c, alpha, g, "ctmat_reserve"));
     RC(ctmul_check_flags("ctmat_reserve", flags, level));
     size_t batch = 0;
     if (!ctmat_batch(m, n, npoly, &batch)) return set_error(MFHE_EINVAL, "ctmat_reserve: m n npoly overflows");
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    if (flags & MFHE_CTMUL_RESCALE) {
-        const uint64_t* rs = nullptr;
-        RC(bconv_table(c, level - 1, 1, 0, level - 1, &rs));
-    }
-    return grow_ws(c, ctmul_ws_words(batch, t.beta, (size_t)g.rows(), level, c->N) * 8);
+    return ctmul_prepare(c, batch, g, alpha, flags, t);
 }
 
 extern "C" int mfhe_ctmat_apply(mfhe_ctx* c, const uint64_t* d_a0, const uint64_t* d_a1, size_t a_row_stride,
@@ -343,37 +330,32 @@ extern "C" int mfhe_ctmat_apply(mfhe_ctx* c, const uint64_t* d_a0, const uint64_
                                 int flags, mfhe_stream_t s) {
     RC(ks_check_ctx(c));
     if (!d_rlk || !d_out0 || !d_out1) return set_error(MFHE_EINVAL, "ctmat_apply: null pointer");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "ctmat_apply: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "ctmat_apply"));
+    RC(ks_check_digits(c, alpha, g, "ctmat_apply"));
     RC(ctmul_check_flags("ctmat_apply", flags, level));
-    const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
+    const size_t N = c->N, lw = (size_t)level * N;
     const CtmatOperands o{d_a0, d_a1, a_row_stride, a_col_stride, a_poly_stride, d_b0, d_b1, b_row_stride,
                           b_col_stride, b_poly_stride, m, n, k};
-    CtmulRange in[5];
+    KsRange in[5];
     RC(ctmat_check_operands("ctmat_apply", o, npoly, lw, in));
     if (out_poly_stride < lw) return set_error(MFHE_EINVAL, "ctmat_apply: output poly stride smaller than level * N");
     size_t batch = 0;
     if (!ctmat_batch(m, n, npoly, &batch)) return set_error(MFHE_EINVAL, "ctmat_apply: m n npoly overflows");
-    const int beta = (level + alpha - 1) / alpha;
-    in[4] = {d_rlk, (size_t)beta * 2 * g.key_rows() * N};   // the digits of the key this level reads
+    in[4] = {d_rlk, (size_t)ks_beta(level, alpha) * 2 * g.key_rows() * N};   // the key's digits read here
     const size_t osp = ks_span(batch, out_poly_stride, lw);
-    const CtmulRange out[2] = {{d_out0, osp}, {d_out1, osp}};
-    RC(ctmul_check_overlap("ctmat_apply", in, 5, out, 2));
+    const KsRange out[2] = {{d_out0, osp}, {d_out1, osp}};
+    RC(ks_check_overlap("ctmat_apply", in, 5, out, 2));
     if (npoly == 0) return MFHE_OK;
     // every table and the workspace before the first launch (nothing to do after mfhe_ctmat_reserve)
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    const uint64_t* rs = nullptr;
-    if (flags & MFHE_CTMUL_RESCALE) RC(bconv_table(c, level - 1, 1, 0, level - 1, &rs));
-    RC(grow_ws(c, ctmul_ws_words(batch, t.beta, rows, level, N) * 8));
+    RC(ctmul_prepare(c, batch, g, alpha, flags, t));
     hipStream_t st = (hipStream_t)s;
-    uint64_t* d2 = (uint64_t*)c->ws + ks_ws_words(batch, t.beta, rows, N);   // [m][n][npoly][level][N]
+    uint64_t* d2 = ctmul_d2(c, batch, t.beta, g);   // [m][n][npoly][level][N]
 
     // entry (i, j) of the outputs and of d2 is polynomials (i n + j) npoly .. of the batch
     const CtmatMatrix d01{(size_t)m, (size_t)n, (size_t)n * npoly * out_poly_stride, npoly * out_poly_stride,
                           out_poly_stride};
     const CtmatMatrix d2s{(size_t)m, (size_t)n, (size_t)n * npoly * lw, npoly * lw, lw};
     RC(launch_ctmat_tensor(c, ctmat_args(o, d_out0, d_out1, d01, d2, d2s, npoly, level, N), st));
-    return ctmul_relin_rescale(c, d_rlk, d_out0, d_out1, out_poly_stride, batch, g, alpha, t, rs, flags, st);
+    return ctmul_relin_rescale(c, d_rlk, d_out0, d_out1, out_poly_stride, batch, g, alpha, t, flags, st);
 }

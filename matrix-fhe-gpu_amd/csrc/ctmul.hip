@@ -133,29 +133,15 @@ static_assert(kCtmulUnroll == 6 && kCtmulUnroll <= kCtmulFold, "pick_ctmul lists
 int launch_ctmul_tensor(mfhe_ctx* c, CtmulArgs a, hipStream_t st) {
     if (a.npoly == 0 || a.ncoeff == 0) return MFHE_OK;
     const bool sq = !a.b0;
-    uint64_t odd = a.ncoeff | a.a_term | a.a_poly | a.d01_poly | a.d2_poly;
-    uintptr_t ptrs = (uintptr_t)a.a0 | (uintptr_t)a.a1 | (uintptr_t)a.d0 | (uintptr_t)a.d1 | (uintptr_t)a.d2;
-    if (!sq) {
-        odd |= a.b_term | a.b_poly;
-        ptrs |= (uintptr_t)a.b0 | (uintptr_t)a.b1;
-    }
-    const bool wide = odd % 2 == 0 && (ptrs & 15) == 0;
-    if (wide) {
-        a.ncoeff /= 2;
-        a.a_term /= 2;
-        a.a_poly /= 2;
-        a.b_term /= 2;
-        a.b_poly /= 2;
-        a.d01_poly /= 2;
-        a.d2_poly /= 2;
-    }
-    const uint32_t block = a.ncoeff >= 256 ? 256 : (uint32_t)((a.ncoeff + 63) / 64 * 64);
-    const uint64_t bx = (a.ncoeff + block - 1) / block;
-    if (bx > 0x7fffffffull || a.level > 65535) return set_error(MFHE_EINVAL, "ctmul_tensor: too large for one launch");
-    const dim3 grid((uint32_t)bx, (uint32_t)a.level, (uint32_t)(a.npoly < 65535 ? a.npoly : 65535));
+    if (sq) a.b_term = a.b_poly = 0;   // unread, and they do not bear on the form
+    const bool wide = ks_wide({&a.ncoeff, &a.a_term, &a.a_poly, &a.b_term, &a.b_poly, &a.d01_poly, &a.d2_poly},
+                              {a.a0, a.a1, a.b0, a.b1, a.d0, a.d1, a.d2});
+    const KsRowGrid rg = ks_row_grid(a.ncoeff);
+    if (rg.bx > 0x7fffffffull || a.level > 65535) return set_error(MFHE_EINVAL, "ctmul_tensor: too large for one launch");
+    const dim3 grid((uint32_t)rg.bx, (uint32_t)a.level, (uint32_t)(a.npoly < 65535 ? a.npoly : 65535));
     const CtmulKernel k = wide ? (sq ? pick_ctmul<2, true>(a.nterms) : pick_ctmul<2, false>(a.nterms))
                                : (sq ? pick_ctmul<1, true>(a.nterms) : pick_ctmul<1, false>(a.nterms));
-    hipLaunchKernelGGL(k, grid, dim3(block), 0, st, a, (const uint64_t*)c->d_dmod);
+    hipLaunchKernelGGL(k, grid, dim3(rg.block), 0, st, a, (const uint64_t*)c->d_dmod);
     MFHE_CHECK_LAUNCH("ctmul_tensor_kernel");
     return MFHE_OK;
 }
@@ -170,7 +156,7 @@ struct CtmulOperands {
 };
 
 // Pointers, term count and strides of the operands (lw = level * N); in[0 .. *nin) = the ranges they span.
-static int ctmul_check_operands(const std::string& w, const CtmulOperands& o, size_t npoly, size_t lw, CtmulRange in[4],
+static int ctmul_check_operands(const std::string& w, const CtmulOperands& o, size_t npoly, size_t lw, KsRange in[4],
                                 int* nin) {
     if (!o.a0 || !o.a1) return set_error(MFHE_EINVAL, w + ": null pointer");
     if (!o.b0 != !o.b1) return set_error(MFHE_EINVAL, w + ": exactly one of d_b0, d_b1 is null");
@@ -190,19 +176,6 @@ static int ctmul_check_operands(const std::string& w, const CtmulOperands& o, si
     return MFHE_OK;
 }
 
-// no output may overlap an input or another output
-int ctmul_check_overlap(const std::string& w, const CtmulRange* in, int nin, const CtmulRange* out, int nout) {
-    for (int k = 0; k < nout; ++k) {
-        for (int i = 0; i < nin; ++i)
-            if (ks_ranges_overlap(in[i].p, in[i].words, out[k].p, out[k].words))
-                return set_error(MFHE_EINVAL, w + ": an input overlaps an output");
-        for (int j = 0; j < k; ++j)
-            if (ks_ranges_overlap(out[j].p, out[j].words, out[k].p, out[k].words))
-                return set_error(MFHE_EINVAL, w + ": the outputs overlap");
-    }
-    return MFHE_OK;
-}
-
 static CtmulArgs ctmul_args(const CtmulOperands& o, uint64_t* d0, uint64_t* d1, size_t d01_poly, uint64_t* d2,
                             size_t d2_poly, size_t npoly, int level, size_t N) {
     CtmulArgs a{};
@@ -214,12 +187,6 @@ static CtmulArgs ctmul_args(const CtmulOperands& o, uint64_t* d0, uint64_t* d1, 
     return a;
 }
 
-// words of mfhe_ctmul_apply's block of the workspace: the key switch's block (the rescale's scratch, 2 npoly level N
-// words, reuses it), then d2 [npoly][level][N]
-size_t ctmul_ws_words(size_t npoly, int beta, size_t rows, int level, size_t N) {
-    return ks_ws_words(npoly, beta, rows, N) + npoly * (size_t)level * N;
-}
-
 int ctmul_check_flags(const char* what, int flags, int level) {
     const std::string w(what);
     if (flags & ~MFHE_CTMUL_RESCALE) return set_error(MFHE_EINVAL, w + ": unknown flag");
@@ -228,41 +195,24 @@ int ctmul_check_flags(const char* what, int flags, int level) {
     return MFHE_OK;
 }
 
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
+int ctmul_prepare(mfhe_ctx* c, size_t npoly, const KsGeom& g, int alpha, int flags, KsTables& t) {
+    const size_t words = ks_ws_words(npoly, ks_beta(g.level, alpha), (size_t)g.rows(), c->N) + npoly * g.level * c->N;
+    return ks_prepare(c, g, alpha, (flags & MFHE_CTMUL_RESCALE) ? kKsRescale : 0, words, t);
+}
 
 int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride,
-                        size_t npoly, const KsGeom& g, int alpha, const KsTables& t, const uint64_t* rs, int flags,
-                        hipStream_t st) {
-    const int level = g.level, special_start = g.special_start, nspecial = g.nspecial;
-    const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
-    const size_t pw = rows * N;                                   // one raised polynomial
-    uint64_t* raised = (uint64_t*)c->ws;                          // [beta][npoly][rows][N]   the key switch's block
-    uint64_t* acc = raised + (size_t)t.beta * npoly * pw;         // [npoly][2][rows][N]
-    uint64_t* scratch = acc + 2 * npoly * pw;                     // 2 npoly * rows * N words
-    uint64_t* d2 = (uint64_t*)c->ws + ks_ws_words(npoly, t.beta, rows, N);   // [npoly][level][N]
+                        size_t npoly, const KsGeom& g, int alpha, const KsTables& t, int flags, hipStream_t st) {
+    const size_t N = c->N, lw = (size_t)g.level * N;
     // the body of mfhe_keyswitch with MFHE_KS_ADD on d2
-    for (int j = 0; j < t.beta; ++j) {
-        const int ds = j * alpha, dc = level - ds < alpha ? level - ds : alpha;
-        RC(ntt_modup_body(c, d2, lw, raised + (size_t)j * npoly * pw, pw, npoly, ds, dc, t.plan[j],
-                          &t.tab[(size_t)3 * j], scratch, st));
-    }
-    KsipArgs a{};
-    a.raised = raised; a.ksk = d_rlk; a.acc = acc;
-    a.digit_stride = npoly * pw; a.poly_stride = pw; a.acc_stride = 2 * pw;
-    a.ncoeff = N; a.npoly = npoly; a.ndigits = t.beta; a.g = g;
-    RC(launch_ksk_inner_product(c, a, st));
-    const uint64_t* cen = nullptr;
-    RC(ntt_moddown_center(c, acc, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
-    uint64_t* outs[2] = {d_out0, d_out1};
-    for (int k = 0; k < 2; ++k)
-        RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_poly_stride,
-                            outs[k], npoly, level, nspecial, t.down, st));
+    RC(ks_switch_body(c, ctmul_d2(c, npoly, t.beta, g), lw, d_rlk, {d_out0, d_out1, out_poly_stride, 3}, npoly, g, alpha,
+                      t, st));
     if (!(flags & MFHE_CTMUL_RESCALE)) return MFHE_OK;
     // The rescale: mfhe_ntt_moddown(keep = level - 1, drop = limb level - 1) in place on each output, its scratch the
     // key switch's block.  The two outputs are one batch of 2 npoly polynomials when one follows the other at the
     // poly stride (any two single polynomials do); the work per polynomial is the same either way.
-    const int keep = level - 1;
+    const int keep = g.level - 1;
     const size_t kw = (size_t)keep * N;
+    const uint64_t *rs = t.rescale, *cen = nullptr;
     uint64_t* lo = d_out0 < d_out1 ? d_out0 : d_out1;
     const size_t gap = (size_t)((d_out0 < d_out1 ? d_out1 : d_out0) - lo);
     const size_t batch_stride = npoly == 1 ? gap : gap == npoly * out_poly_stride ? out_poly_stride : 0;
@@ -271,10 +221,9 @@ int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, ui
         RC(ntt_moddown_center(c, lo, batch_stride, 2 * npoly, keep, keep, 1, rs, ws, &cen, st));
         return launch_sub_scale(c, lo, batch_stride, cen, kw, lo, batch_stride, nullptr, 2 * npoly, keep, 1, rs, st);
     }
-    for (int k = 0; k < 2; ++k) {
-        RC(ntt_moddown_center(c, outs[k], out_poly_stride, npoly, keep, keep, 1, rs, ws, &cen, st));
-        RC(launch_sub_scale(c, outs[k], out_poly_stride, cen, kw, outs[k], out_poly_stride, nullptr, npoly, keep, 1,
-                            rs, st));
+    for (uint64_t* o : {d_out0, d_out1}) {
+        RC(ntt_moddown_center(c, o, out_poly_stride, npoly, keep, keep, 1, rs, ws, &cen, st));
+        RC(launch_sub_scale(c, o, out_poly_stride, cen, kw, o, out_poly_stride, nullptr, npoly, keep, 1, rs, st));
     }
     return MFHE_OK;
 }
@@ -293,14 +242,14 @@ extern "C" int mfhe_ctmul_tensor(mfhe_ctx* c, const uint64_t* d_a0, const uint64
     if (level < 1 || level > c->L) return set_error(MFHE_EINVAL, "ctmul_tensor: level outside the context");
     const size_t N = c->N, lw = (size_t)level * N;
     const CtmulOperands o{d_a0, d_a1, a_term_stride, a_poly_stride, d_b0, d_b1, b_term_stride, b_poly_stride, nterms};
-    CtmulRange in[4];
+    KsRange in[4];
     int nin = 0;
     RC(ctmul_check_operands("ctmul_tensor", o, npoly, lw, in, &nin));
     if (d01_poly_stride < lw || d2_poly_stride < lw)
         return set_error(MFHE_EINVAL, "ctmul_tensor: output poly stride smaller than level * N");
     const size_t osp = ks_span(npoly, d01_poly_stride, lw);
-    const CtmulRange out[3] = {{d_d0, osp}, {d_d1, osp}, {d_d2, ks_span(npoly, d2_poly_stride, lw)}};
-    RC(ctmul_check_overlap("ctmul_tensor", in, nin, out, 3));
+    const KsRange out[3] = {{d_d0, osp}, {d_d1, osp}, {d_d2, ks_span(npoly, d2_poly_stride, lw)}};
+    RC(ks_check_overlap("ctmul_tensor", in, nin, out, 3));
     if (npoly == 0) return MFHE_OK;
     return launch_ctmul_tensor(c, ctmul_args(o, d_d0, d_d1, d01_poly_stride, d_d2, d2_poly_stride, npoly, level, N),
                                (hipStream_t)s);
@@ -309,17 +258,11 @@ extern "C" int mfhe_ctmul_tensor(mfhe_ctx* c, const uint64_t* d_a0, const uint64
 extern "C" int mfhe_ctmul_reserve(mfhe_ctx* c, size_t npoly, int level, int key_level, int alpha, int special_start,
                                   int nspecial, int flags) {
     RC(ks_check_ctx(c));
-    if (alpha < 1) return set_error(MFHE_EINVAL, "ctmul_reserve: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "ctmul_reserve"));
+    RC(ks_check_digits(c, alpha, g, "ctmul_reserve"));
     RC(ctmul_check_flags("ctmul_reserve", flags, level));
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    if (flags & MFHE_CTMUL_RESCALE) {
-        const uint64_t* rs = nullptr;
-        RC(bconv_table(c, level - 1, 1, 0, level - 1, &rs));
-    }
-    return grow_ws(c, ctmul_ws_words(npoly, t.beta, (size_t)g.rows(), level, c->N) * 8);
+    return ctmul_prepare(c, npoly, g, alpha, flags, t);
 }
 
 extern "C" int mfhe_ctmul_apply(mfhe_ctx* c, const uint64_t* d_a0, const uint64_t* d_a1, size_t a_term_stride,
@@ -329,31 +272,25 @@ extern "C" int mfhe_ctmul_apply(mfhe_ctx* c, const uint64_t* d_a0, const uint64_
                                 int alpha, int special_start, int nspecial, int flags, mfhe_stream_t s) {
     RC(ks_check_ctx(c));
     if (!d_rlk || !d_out0 || !d_out1) return set_error(MFHE_EINVAL, "ctmul_apply: null pointer");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "ctmul_apply: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "ctmul_apply"));
+    RC(ks_check_digits(c, alpha, g, "ctmul_apply"));
     RC(ctmul_check_flags("ctmul_apply", flags, level));
-    const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
+    const size_t N = c->N, lw = (size_t)level * N;
     const CtmulOperands o{d_a0, d_a1, a_term_stride, a_poly_stride, d_b0, d_b1, b_term_stride, b_poly_stride, nterms};
-    CtmulRange in[5];
+    KsRange in[5];
     int nin = 0;
     RC(ctmul_check_operands("ctmul_apply", o, npoly, lw, in, &nin));
     if (out_poly_stride < lw) return set_error(MFHE_EINVAL, "ctmul_apply: output poly stride smaller than level * N");
-    const int beta = (level + alpha - 1) / alpha;
-    in[nin++] = {d_rlk, (size_t)beta * 2 * g.key_rows() * N};   // the digits of the key this level reads
+    in[nin++] = {d_rlk, (size_t)ks_beta(level, alpha) * 2 * g.key_rows() * N};   // the key's digits read here
     const size_t osp = ks_span(npoly, out_poly_stride, lw);
-    const CtmulRange out[2] = {{d_out0, osp}, {d_out1, osp}};
-    RC(ctmul_check_overlap("ctmul_apply", in, nin, out, 2));
+    const KsRange out[2] = {{d_out0, osp}, {d_out1, osp}};
+    RC(ks_check_overlap("ctmul_apply", in, nin, out, 2));
     if (npoly == 0) return MFHE_OK;
     // every table and the workspace before the first launch (nothing to do after mfhe_ctmul_reserve)
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    const uint64_t* rs = nullptr;
-    if (flags & MFHE_CTMUL_RESCALE) RC(bconv_table(c, level - 1, 1, 0, level - 1, &rs));
-    RC(grow_ws(c, ctmul_ws_words(npoly, t.beta, rows, level, N) * 8));
+    RC(ctmul_prepare(c, npoly, g, alpha, flags, t));
     hipStream_t st = (hipStream_t)s;
-    uint64_t* d2 = (uint64_t*)c->ws + ks_ws_words(npoly, t.beta, rows, N);   // [npoly][level][N]
-
+    uint64_t* d2 = ctmul_d2(c, npoly, t.beta, g);   // [npoly][level][N]
     RC(launch_ctmul_tensor(c, ctmul_args(o, d_out0, d_out1, out_poly_stride, d2, lw, npoly, level, N), st));
-    return ctmul_relin_rescale(c, d_rlk, d_out0, d_out1, out_poly_stride, npoly, g, alpha, t, rs, flags, st);
+    return ctmul_relin_rescale(c, d_rlk, d_out0, d_out1, out_poly_stride, npoly, g, alpha, t, flags, st);
 }

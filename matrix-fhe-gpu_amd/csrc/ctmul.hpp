@@ -55,24 +55,19 @@ struct CtmulArgs {
 int launch_ctmul_tensor(mfhe_ctx* c, CtmulArgs a, hipStream_t st);
 
 // ---- shared with ctmat.hip ----
-// A range of device words, for the overlap checks.
-struct CtmulRange {
-    const uint64_t* p;
-    size_t words;
-};
-// no output may overlap an input or another output
-int ctmul_check_overlap(const std::string& w, const CtmulRange* in, int nin, const CtmulRange* out, int nout);
 // the flags of a driver: unknown ones, and MFHE_CTMUL_RESCALE at level 1
 int ctmul_check_flags(const char* what, int flags, int level);
-// words of a driver's block of the workspace: the key switch's block (the rescale's scratch, 2 npoly level N words,
-// reuses it), then d2 [npoly][level][N]
-size_t ctmul_ws_words(size_t npoly, int beta, size_t rows, int level, size_t N);
+// ks_prepare for a driver's block of the workspace: the key switch's block (the rescale's scratch, 2 npoly level N
+// words, reuses it), then d2 [npoly][level][N]; with MFHE_CTMUL_RESCALE the rescale's table as well
+int ctmul_prepare(mfhe_ctx* c, size_t npoly, const KsGeom& g, int alpha, int flags, KsTables& t);
+// d2 of a driver, dense behind the key switch's block
+inline uint64_t* ctmul_d2(const mfhe_ctx* c, size_t npoly, int beta, const KsGeom& g) {
+    return (uint64_t*)c->ws + ks_ws(npoly, beta, (size_t)g.rows(), c->N).end;
+}
 // The tail of a driver once the tensor sum has left d0, d1 in the outputs ([npoly][level][N] at out_poly_stride) and
-// d2 dense behind the key switch's block of the workspace: the body of mfhe_keyswitch with MFHE_KS_ADD on d2, then
-// with MFHE_CTMUL_RESCALE (rs: the table of limb level - 1 -> [0, level - 1)) the ModDown of both outputs in place.
-// Tables built and workspace grown by the caller.
+// d2 dense at ctmul_d2: the body of mfhe_keyswitch with MFHE_KS_ADD on d2, then with MFHE_CTMUL_RESCALE the ModDown of
+// both outputs by limb level - 1 in place.  ctmul_prepare done by the caller.
 int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride,
-                        size_t npoly, const KsGeom& g, int alpha, const KsTables& t, const uint64_t* rs, int flags,
-                        hipStream_t st);
+                        size_t npoly, const KsGeom& g, int alpha, const KsTables& t, int flags, hipStream_t st);
 
 }  // namespace mfhe

@@ -13,6 +13,7 @@
 
 #include <cmath>
 
+#include "bconv.hpp"
 #include "cdft.hpp"
 #include "mfhe_ctx.hpp"
 #include "ring_row.hpp"
@@ -499,16 +500,7 @@ static size_t ws_need(const mfhe_ctx* c) {
     return 10 * g.words * 8 + g.cnt * (size_t)c->W * 8 + 4 * g.cnt * 16 + 2 * g.cnt + (64 << 10);
 }
 
-static int ensure_ws(mfhe_ctx* c) {
-    const size_t need = ws_need(c);
-    if (c->ws_bytes >= need) return MFHE_OK;
-    if (c->ws) MFHE_HIP(hipFree(c->ws));
-    c->ws = nullptr;
-    c->ws_bytes = 0;
-    MFHE_HIP(hipMalloc(&c->ws, need));
-    c->ws_bytes = need;
-    return MFHE_OK;
-}
+static int ensure_ws(mfhe_ctx* c) { return grow_ws(c, ws_need(c)); }
 
 struct Bump {
     char* p;
@@ -522,7 +514,6 @@ struct Bump {
 
 // W-CRT forward: B matrix-major [r][L][pos] (or vector [r][L][x]); C in the requested layout
 enum class WOut { Poly, Matrix, Vector };
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 // i8 MFMA operands for A = V or V^-1 (wcrt_gemm.hpp); leaves a on the VALU kernel when unavailable.  slot 1: the side
 // stream's digit planes (HeFork)

@@ -169,32 +169,20 @@ __global__ __launch_bounds__(256) void ksk_assemble_kernel(const uint64_t* __res
 
 using KsipKernel = void (*)(KsipArgs, const uint64_t*);
 
-template <int V>
+// PERM: the instantiations that read the raised digits through a Galois gather
+template <int V, bool PERM>
 static KsipKernel pick_ksip(int nd) {
     switch (nd) {
-        case 1: return ksk_inner_product_kernel<1, V, false>;
-        case 2: return ksk_inner_product_kernel<2, V, false>;
-        case 3: return ksk_inner_product_kernel<3, V, false>;
-        case 4: return ksk_inner_product_kernel<4, V, false>;
-        case 5: return ksk_inner_product_kernel<5, V, false>;
-        case 6: return ksk_inner_product_kernel<6, V, false>;
-        default: return ksk_inner_product_kernel<0, V, false>;
+        case 1: return ksk_inner_product_kernel<1, V, PERM>;
+        case 2: return ksk_inner_product_kernel<2, V, PERM>;
+        case 3: return ksk_inner_product_kernel<3, V, PERM>;
+        case 4: return ksk_inner_product_kernel<4, V, PERM>;
+        case 5: return ksk_inner_product_kernel<5, V, PERM>;
+        case 6: return ksk_inner_product_kernel<6, V, PERM>;
+        default: return ksk_inner_product_kernel<0, V, PERM>;
     }
 }
-// the instantiations that read the raised digits through a Galois gather
-template <int V>
-static KsipKernel pick_ksip_galois(int nd) {
-    switch (nd) {
-        case 1: return ksk_inner_product_kernel<1, V, true>;
-        case 2: return ksk_inner_product_kernel<2, V, true>;
-        case 3: return ksk_inner_product_kernel<3, V, true>;
-        case 4: return ksk_inner_product_kernel<4, V, true>;
-        case 5: return ksk_inner_product_kernel<5, V, true>;
-        case 6: return ksk_inner_product_kernel<6, V, true>;
-        default: return ksk_inner_product_kernel<0, V, true>;
-    }
-}
-static_assert(kKsipUnroll == 6, "pick_ksip and pick_ksip_galois list the unrolled digit counts");
+static_assert(kKsipUnroll == 6, "pick_ksip lists the unrolled digit counts");
 
 int launch_ksk_inner_product(mfhe_ctx* c, KsipArgs a, hipStream_t st) {
     if (a.npoly == 0 || a.ncoeff == 0) return MFHE_OK;
@@ -204,29 +192,16 @@ int launch_ksk_inner_product(mfhe_ctx* c, KsipArgs a, hipStream_t st) {
         if ((1ull << a.log_n) != a.ncoeff || a.log_n > 30 || !(a.galois_elt & 1u) || a.galois_elt >= 2 * a.ncoeff)
             return set_error(MFHE_EINVAL, "ksk_inner_product: Galois element is not an odd integer in [1, 2 N)");
     }
-    const bool wide = a.ncoeff % 2 == 0 && a.digit_stride % 2 == 0 && a.poly_stride % 2 == 0 && a.acc_stride % 2 == 0 &&
-                      (((uintptr_t)a.raised | (uintptr_t)a.ksk | (uintptr_t)a.acc) & 15) == 0;
-    if (wide) {
-        a.ncoeff /= 2;
-        a.digit_stride /= 2;
-        a.poly_stride /= 2;
-        a.acc_stride /= 2;
-    }
-    const uint32_t block = a.ncoeff >= 256 ? 256 : (uint32_t)((a.ncoeff + 63) / 64 * 64);
-    const uint64_t bx = (a.ncoeff + block - 1) / block;
+    const bool wide = ks_wide({&a.ncoeff, &a.digit_stride, &a.poly_stride, &a.acc_stride}, {a.raised, a.ksk, a.acc});
+    const KsRowGrid rg = ks_row_grid(a.ncoeff);
     const uint64_t rows = (uint64_t)a.g.rows();
-    if (bx > 0x7fffffffull || rows > 65535) return set_error(MFHE_EINVAL, "ksk_inner_product: too large for one launch");
-    // A thread keeps its key slice across `prun` polynomials: as long a run as still leaves about 4096 workgroups
-    // (16 per CU) in the grid, and never shorter than kKsipMinRun (or the batch).
-    uint64_t runs = 4096 / (bx * rows);
-    runs = runs < 1 ? 1 : runs;
-    a.prun = (a.npoly + runs - 1) / runs;
-    if (a.prun < kKsipMinRun) a.prun = a.npoly < kKsipMinRun ? a.npoly : kKsipMinRun;
-    if ((a.npoly + a.prun - 1) / a.prun > 65535) a.prun = (a.npoly + 65534) / 65535;   // grid z limit
-    runs = (a.npoly + a.prun - 1) / a.prun;
-    const KsipKernel k = a.galois_elt ? (wide ? pick_ksip_galois<2>(a.ndigits) : pick_ksip_galois<1>(a.ndigits))
-                                      : (wide ? pick_ksip<2>(a.ndigits) : pick_ksip<1>(a.ndigits));
-    hipLaunchKernelGGL(k, dim3((uint32_t)bx, (uint32_t)rows, (uint32_t)runs), dim3(block), 0, st, a,
+    if (rg.bx > 0x7fffffffull || rows > 65535)
+        return set_error(MFHE_EINVAL, "ksk_inner_product: too large for one launch");
+    const KsRuns run = ks_runs(a.npoly, rg.bx, rows, kKsipMinRun);   // a thread keeps its key slice across a run
+    a.prun = run.prun;
+    const KsipKernel k = a.galois_elt ? (wide ? pick_ksip<2, true>(a.ndigits) : pick_ksip<1, true>(a.ndigits))
+                                      : (wide ? pick_ksip<2, false>(a.ndigits) : pick_ksip<1, false>(a.ndigits));
+    hipLaunchKernelGGL(k, dim3((uint32_t)rg.bx, (uint32_t)rows, (uint32_t)run.runs), dim3(rg.block), 0, st, a,
                        (const uint64_t*)c->d_dmod);
     MFHE_CHECK_LAUNCH("ksk_inner_product_kernel");
     return MFHE_OK;
@@ -285,34 +260,114 @@ int ks_check_galois(const mfhe_ctx* c, int galois_elt, const char* what) {
     return MFHE_OK;
 }
 
-// words spanned by npoly blocks of `words` words, `stride` apart
-size_t ks_span(size_t npoly, size_t stride, size_t words) { return npoly ? (npoly - 1) * stride + words : 0; }
-bool ks_ranges_overlap(const uint64_t* a, size_t na, const uint64_t* b, size_t nb) {
-    return na && nb && a < b + nb && b < a + na;
+int ks_check_digits(const mfhe_ctx* c, int alpha, const KsGeom& g, const char* what) {
+    if (alpha < 1) return set_error(MFHE_EINVAL, std::string(what) + ": alpha < 1");
+    return ks_check_geom(c, g, what);
 }
 
-// words of the key switch's block of the workspace: raised digits, acc, the inner calls' scratch (the ModDown of both
-// components at once: 2 npoly polynomials)
-size_t ks_ws_words(size_t npoly, int beta, size_t rows, size_t N) { return ((size_t)beta + 4) * npoly * rows * N; }
+int ks_check_overlap(const std::string& w, const KsRange* in, size_t nin, const KsRange* out, size_t nout) {
+    const int o = ks_find_overlap(in, nin, out, nout);
+    if (o == kKsNoOverlap) return MFHE_OK;
+    return set_error(MFHE_EINVAL, w + (o == kKsInputOverlap ? ": an input overlaps an output" : ": the outputs overlap"));
+}
+
+// ---- tables and workspace ----
+static int ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t) {
+    t.beta = ks_beta(g.level, alpha);
+    t.plan.assign(t.beta, ModUpPlan{});
+    t.tab.assign((size_t)3 * t.beta, nullptr);
+    for (int j = 0; j < t.beta; ++j) {
+        const int ds = j * alpha, dc = g.level - ds < alpha ? g.level - ds : alpha;
+        RC(check_modup(c, g.level, ds, dc, g.special_start, g.nspecial, t.plan[j]));
+        RC(ntt_modup_tables(c, ds, dc, t.plan[j], &t.tab[(size_t)3 * j]));
+    }
+    return bconv_table(c, g.special_start, g.nspecial, 0, g.level, &t.down);
+}
+
+int ks_prepare(mfhe_ctx* c, const KsGeom& g, int alpha, int extra, size_t ws_words, KsTables& t) {
+    RC(ks_tables(c, g, alpha, t));
+    if (extra & kKsRescale) RC(bconv_table(c, g.level - 1, 1, 0, g.level - 1, &t.rescale));
+    if (extra & kKsPmod) RC(ksk_pmod_table(c, g.key_level, g.special_start, g.nspecial, &t.pmod));
+    return grow_ws(c, ws_words * 8);
+}
+
+int ks_reserve(mfhe_ctx* c, size_t npoly, const KsGeom& g, int alpha, const char* what) {
+    RC(ks_check_ctx(c));
+    RC(ks_check_digits(c, alpha, g, what));
+    KsTables t;
+    return ks_prepare(c, g, alpha, 0, ks_ws_words(npoly, ks_beta(g.level, alpha), (size_t)g.rows(), c->N), t);
+}
+
+// ---- the pipeline ----
+int raise_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, uint64_t* raised, size_t digit_stride,
+               size_t poly_stride, size_t npoly, const KsGeom& g, int alpha, const KsTables& t, uint64_t* scratch,
+               hipStream_t st) {
+    for (int j = 0; j < t.beta; ++j) {
+        const int ds = j * alpha, dc = g.level - ds < alpha ? g.level - ds : alpha;
+        RC(ntt_modup_body(c, d_in, in_stride, raised + (size_t)j * digit_stride, poly_stride, npoly, ds, dc, t.plan[j],
+                          &t.tab[(size_t)3 * j], scratch, st));
+    }
+    return MFHE_OK;
+}
+
+int ks_raise_ws(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, size_t npoly, const KsGeom& g, int alpha,
+                const KsTables& t, hipStream_t st) {
+    const size_t pw = (size_t)g.rows() * c->N;
+    const KsWs w = ks_ws(npoly, t.beta, (size_t)g.rows(), c->N);
+    uint64_t* ws = (uint64_t*)c->ws;
+    return raise_body(c, d_in, in_stride, ws + w.raised, npoly * pw, pw, npoly, g, alpha, t, ws + w.scratch, st);
+}
+
+int ks_inner_product(mfhe_ctx* c, const KsRaised& x, const uint64_t* d_ksk, uint64_t* d_acc, size_t acc_stride,
+                     size_t npoly, int ndigits, const KsGeom& g, uint32_t galois_elt, hipStream_t st) {
+    KsipArgs a{};
+    a.raised = x.p; a.ksk = d_ksk; a.acc = d_acc;
+    a.digit_stride = x.digit_stride; a.poly_stride = x.poly_stride; a.acc_stride = acc_stride;
+    a.ncoeff = c->N; a.npoly = npoly; a.ndigits = ndigits; a.g = g; a.galois_elt = galois_elt;
+    return launch_ksk_inner_product(c, a, st);
+}
+
+int ks_moddown_pair(mfhe_ctx* c, const uint64_t* acc, uint64_t* scratch, const KsOut& o, size_t npoly, const KsGeom& g,
+                    const KsTables& t, hipStream_t st) {
+    const size_t pw = (size_t)g.rows() * c->N, lw = (size_t)g.level * c->N;
+    const uint64_t* cen = nullptr;
+    RC(ntt_moddown_center(c, acc, pw, 2 * npoly, g.level, g.special_start, g.nspecial, t.down, scratch, &cen, st));
+    uint64_t* outs[2] = {o.out0, o.out1};
+    for (int k = 0; k < 2; ++k)
+        RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], o.stride,
+                            (o.add >> k & 1) ? outs[k] : nullptr, npoly, g.level, g.nspecial, t.down, st));
+    return MFHE_OK;
+}
+
+int ks_apply_raised(mfhe_ctx* c, const KsRaised& x, const uint64_t* d_ksk, const KsOut& o, size_t npoly,
+                    const KsGeom& g, const KsTables& t, uint32_t galois_elt, hipStream_t st) {
+    const size_t pw = (size_t)g.rows() * c->N;
+    const KsWs w = ks_ws(npoly, t.beta, (size_t)g.rows(), c->N);
+    uint64_t* ws = (uint64_t*)c->ws;
+    RC(ks_inner_product(c, x, d_ksk, ws + w.acc, 2 * pw, npoly, t.beta, g, galois_elt, st));
+    return ks_moddown_pair(c, ws + w.acc, ws + w.scratch, o, npoly, g, t, st);
+}
+
+int ks_switch_body(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const uint64_t* d_ksk, const KsOut& o,
+                   size_t npoly, const KsGeom& g, int alpha, const KsTables& t, hipStream_t st) {
+    RC(ks_raise_ws(c, d_in, in_stride, npoly, g, alpha, t, st));
+    return ks_apply_raised(c, ks_ws_raised(c, npoly, g), d_ksk, o, npoly, g, t, 0, st);
+}
 
 }  // namespace mfhe
 
 using namespace mfhe;
-
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 extern "C" int mfhe_ksk_assemble(mfhe_ctx* c, const uint64_t* d_s_from, const uint64_t* d_s_to, const uint64_t* d_a,
                                  const uint64_t* d_e, uint64_t* d_ksk, int key_level, int alpha, int special_start,
                                  int nspecial, mfhe_stream_t s) {
     RC(ks_check_ctx(c));
     if (!d_s_from || !d_s_to || !d_a || !d_e || !d_ksk) return set_error(MFHE_EINVAL, "ksk_assemble: null pointer");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "ksk_assemble: alpha < 1");
     const KsGeom g{key_level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "ksk_assemble"));
+    RC(ks_check_digits(c, alpha, g, "ksk_assemble"));
     const uint64_t* pmod = nullptr;
     RC(ksk_pmod_table(c, key_level, special_start, nspecial, &pmod));
-    const int beta = (key_level + alpha - 1) / alpha;
-    const uint64_t total = (uint64_t)beta * g.key_rows() * c->N;
+    const uint64_t total = (uint64_t)ks_beta(key_level, alpha) * g.key_rows() * c->N;
     const uint64_t blocks = (total + 255) / 256;
     if (blocks > 0x7fffffffull) return set_error(MFHE_EINVAL, "ksk_assemble: too many coefficients for one launch");
     hipLaunchKernelGGL(ksk_assemble_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)s, d_s_from, d_s_to, d_a,
@@ -337,11 +392,8 @@ static int ksk_inner_product_checked(mfhe_ctx* c, const uint64_t* d_raised, size
         return set_error(MFHE_EINVAL, "ksk_inner_product: poly stride smaller than rows * N");
     if (npoly && digit_stride < ks_span(npoly, poly_stride, rows * N))
         return set_error(MFHE_EINVAL, "ksk_inner_product: digit stride smaller than the polynomials of a digit");
-    KsipArgs a{};
-    a.raised = d_raised; a.ksk = d_ksk; a.acc = d_acc;
-    a.digit_stride = digit_stride; a.poly_stride = poly_stride; a.acc_stride = acc_poly_stride;
-    a.ncoeff = N; a.npoly = npoly; a.ndigits = ndigits; a.g = g; a.galois_elt = galois_elt;
-    return launch_ksk_inner_product(c, a, (hipStream_t)s);
+    return ks_inner_product(c, {d_raised, digit_stride, poly_stride}, d_ksk, d_acc, acc_poly_stride, npoly, ndigits, g,
+                            galois_elt, (hipStream_t)s);
 }
 
 extern "C" int mfhe_ksk_inner_product(mfhe_ctx* c, const uint64_t* d_raised, size_t digit_stride, size_t poly_stride,
@@ -363,27 +415,9 @@ extern "C" int mfhe_ksk_inner_product_galois(mfhe_ctx* c, const uint64_t* d_rais
                                      ndigits, level, key_level, special_start, nspecial, (uint32_t)galois_elt, s);
 }
 
-int mfhe::ks_tables(mfhe_ctx* c, const KsGeom& g, int alpha, KsTables& t) {
-    t.beta = (g.level + alpha - 1) / alpha;
-    t.plan.assign(t.beta, ModUpPlan{});
-    t.tab.assign((size_t)3 * t.beta, nullptr);
-    for (int j = 0; j < t.beta; ++j) {
-        const int ds = j * alpha, dc = g.level - ds < alpha ? g.level - ds : alpha;
-        RC(check_modup(c, g.level, ds, dc, g.special_start, g.nspecial, t.plan[j]));
-        RC(ntt_modup_tables(c, ds, dc, t.plan[j], &t.tab[(size_t)3 * j]));
-    }
-    return bconv_table(c, g.special_start, g.nspecial, 0, g.level, &t.down);
-}
-
 extern "C" int mfhe_keyswitch_reserve(mfhe_ctx* c, size_t npoly, int level, int key_level, int alpha,
                                       int special_start, int nspecial) {
-    RC(ks_check_ctx(c));
-    if (alpha < 1) return set_error(MFHE_EINVAL, "keyswitch_reserve: alpha < 1");
-    const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "keyswitch_reserve"));
-    KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    return grow_ws(c, ks_ws_words(npoly, t.beta, (size_t)g.rows(), c->N) * 8);
+    return ks_reserve(c, npoly, {level, key_level, special_start, nspecial}, alpha, "keyswitch_reserve");
 }
 
 extern "C" int mfhe_keyswitch(mfhe_ctx* c, const uint64_t* d_in, size_t in_stride, const uint64_t* d_ksk,
@@ -391,42 +425,17 @@ extern "C" int mfhe_keyswitch(mfhe_ctx* c, const uint64_t* d_in, size_t in_strid
                               int key_level, int alpha, int special_start, int nspecial, int flags, mfhe_stream_t s) {
     RC(ks_check_ctx(c));
     if (!d_in || !d_ksk || !d_out0 || !d_out1) return set_error(MFHE_EINVAL, "keyswitch: null pointer");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "keyswitch: alpha < 1");
-    if (flags & ~MFHE_KS_ADD) return set_error(MFHE_EINVAL, "keyswitch: unknown flag");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "keyswitch"));
-    const size_t N = c->N, rows = (size_t)g.rows(), lw = (size_t)level * N;
+    RC(ks_check_digits(c, alpha, g, "keyswitch"));
+    if (flags & ~MFHE_KS_ADD) return set_error(MFHE_EINVAL, "keyswitch: unknown flag");
+    const size_t N = c->N, lw = (size_t)level * N;
     if (in_stride < lw || out_stride < lw) return set_error(MFHE_EINVAL, "keyswitch: poly stride smaller than level * N");
     const size_t isp = ks_span(npoly, in_stride, lw), osp = ks_span(npoly, out_stride, lw);
-    if (ks_ranges_overlap(d_in, isp, d_out0, osp) || ks_ranges_overlap(d_in, isp, d_out1, osp))
-        return set_error(MFHE_EINVAL, "keyswitch: the input overlaps an output");
-    if (ks_ranges_overlap(d_out0, osp, d_out1, osp)) return set_error(MFHE_EINVAL, "keyswitch: the outputs overlap");
+    RC(ks_check_overlap("keyswitch", {{d_in, isp}}, {{d_out0, osp}, {d_out1, osp}}));
     if (npoly == 0) return MFHE_OK;
     // every table and the workspace before the first launch (nothing to do after mfhe_keyswitch_reserve)
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    RC(grow_ws(c, ks_ws_words(npoly, t.beta, rows, N) * 8));
-    hipStream_t st = (hipStream_t)s;
-    const size_t pw = rows * N;                                   // one raised polynomial
-    uint64_t* raised = (uint64_t*)c->ws;                          // [beta][npoly][rows][N]
-    uint64_t* acc = raised + (size_t)t.beta * npoly * pw;         // [npoly][2][rows][N]
-    uint64_t* scratch = acc + 2 * npoly * pw;                     // 2 npoly * rows * N words
-    for (int j = 0; j < t.beta; ++j) {
-        const int ds = j * alpha, dc = level - ds < alpha ? level - ds : alpha;
-        RC(ntt_modup_body(c, d_in, in_stride, raised + (size_t)j * npoly * pw, pw, npoly, ds, dc, t.plan[j],
-                          &t.tab[(size_t)3 * j], scratch, st));
-    }
-    KsipArgs a{};
-    a.raised = raised; a.ksk = d_ksk; a.acc = acc;
-    a.digit_stride = npoly * pw; a.poly_stride = pw; a.acc_stride = 2 * pw;
-    a.ncoeff = N; a.npoly = npoly; a.ndigits = t.beta; a.g = g;
-    RC(launch_ksk_inner_product(c, a, st));
-    // ModDown of both components as one batch of 2 npoly polynomials, then one tail per component
-    const uint64_t* cen = nullptr;
-    RC(ntt_moddown_center(c, acc, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
-    uint64_t* outs[2] = {d_out0, d_out1};
-    for (int k = 0; k < 2; ++k)
-        RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_stride,
-                            (flags & MFHE_KS_ADD) ? outs[k] : nullptr, npoly, level, nspecial, t.down, st));
-    return MFHE_OK;
+    RC(ks_prepare(c, g, alpha, 0, ks_ws_words(npoly, ks_beta(level, alpha), (size_t)g.rows(), N), t));
+    const KsOut out{d_out0, d_out1, out_stride, (flags & MFHE_KS_ADD) ? 3 : 0};
+    return ks_switch_body(c, d_in, in_stride, d_ksk, out, npoly, g, alpha, t, (hipStream_t)s);
 }

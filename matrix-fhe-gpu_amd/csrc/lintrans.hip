@@ -169,30 +169,16 @@ static_assert(kLtUnroll == 8, "pick_lt_mac lists the unrolled term counts");
 
 int launch_lt_pt_mac(mfhe_ctx* c, LtMacArgs a, size_t npoly, hipStream_t st) {
     if (npoly == 0 || a.ncoeff == 0) return MFHE_OK;
-    const bool wide = a.ncoeff % 2 == 0 && a.slot_stride % 2 == 0 && a.poly_stride % 2 == 0 && a.pt_stride % 2 == 0 &&
-                      a.acc_stride % 2 == 0 && (((uintptr_t)a.u | (uintptr_t)a.pt | (uintptr_t)a.acc) & 15) == 0;
-    if (wide) {
-        a.ncoeff /= 2;
-        a.slot_stride /= 2;
-        a.poly_stride /= 2;
-        a.pt_stride /= 2;
-        a.acc_stride /= 2;
-    }
-    const uint32_t block = a.ncoeff >= 256 ? 256 : (uint32_t)((a.ncoeff + 63) / 64 * 64);
-    const uint64_t bx = (a.ncoeff + block - 1) / block;
+    const bool wide = ks_wide({&a.ncoeff, &a.slot_stride, &a.poly_stride, &a.pt_stride, &a.acc_stride},
+                              {a.u, a.pt, a.acc});
+    const KsRowGrid rg = ks_row_grid(a.ncoeff);
     const uint64_t rows = (uint64_t)(a.level + a.nspecial);
-    if (bx > 0x7fffffffull || rows > 65535) return set_error(MFHE_EINVAL, "lt_pt_mac: too large for one launch");
-    // A thread keeps its plaintext slices across `prun` pairs: as long a run as still leaves about 4096 workgroups
-    // (16 per CU) in the grid, and never shorter than kLtMinRun (or the batch).
+    if (rg.bx > 0x7fffffffull || rows > 65535) return set_error(MFHE_EINVAL, "lt_pt_mac: too large for one launch");
     a.npairs = 2 * (uint64_t)npoly;
-    uint64_t runs = 4096 / (bx * rows);
-    runs = runs < 1 ? 1 : runs;
-    a.prun = (a.npairs + runs - 1) / runs;
-    if (a.prun < kLtMinRun) a.prun = a.npairs < kLtMinRun ? a.npairs : kLtMinRun;
-    if ((a.npairs + a.prun - 1) / a.prun > 65535) a.prun = (a.npairs + 65534) / 65535;   // grid z limit
-    runs = (a.npairs + a.prun - 1) / a.prun;
+    const KsRuns run = ks_runs(a.npairs, rg.bx, rows, kLtMinRun);   // a thread keeps its plaintext slices across a run
+    a.prun = run.prun;
     const LtMacKernel k = wide ? pick_lt_mac<2>(a.nterms) : pick_lt_mac<1>(a.nterms);
-    hipLaunchKernelGGL(k, dim3((uint32_t)bx, (uint32_t)rows, (uint32_t)runs), dim3(block), 0, st, a,
+    hipLaunchKernelGGL(k, dim3((uint32_t)rg.bx, (uint32_t)rows, (uint32_t)run.runs), dim3(rg.block), 0, st, a,
                        (const uint64_t*)c->d_dmod);
     MFHE_CHECK_LAUNCH("lt_pt_mac_kernel");
     return MFHE_OK;
@@ -202,20 +188,13 @@ int launch_lt_c0(mfhe_ctx* c, const uint64_t* src, size_t src_stride, uint64_t* 
                  int level, int nrows, const uint64_t* pmod, uint32_t galois_elt, bool add, hipStream_t st) {
     uint64_t ncoeff = c->N;
     if (npoly == 0 || nrows == 0) return MFHE_OK;
-    const bool wide = ncoeff % 2 == 0 && src_stride % 2 == 0 && u_stride % 2 == 0 &&
-                      (((uintptr_t)src | (uintptr_t)u) & 15) == 0;
-    if (wide) {
-        ncoeff /= 2;
-        src_stride /= 2;
-        u_stride /= 2;
-    }
-    const uint32_t block = ncoeff >= 256 ? 256 : (uint32_t)((ncoeff + 63) / 64 * 64);
-    const uint64_t bx = (ncoeff + block - 1) / block;
-    if (bx > 0x7fffffffull || nrows > 65535) return set_error(MFHE_EINVAL, "lt_baby_step: too large for one launch");
-    const dim3 grid((uint32_t)bx, (uint32_t)nrows, (uint32_t)(npoly < 65535 ? npoly : 65535));
+    const bool wide = ks_wide({&ncoeff, &src_stride, &u_stride}, {src, u});
+    const KsRowGrid rg = ks_row_grid(ncoeff);
+    if (rg.bx > 0x7fffffffull || nrows > 65535) return set_error(MFHE_EINVAL, "lt_baby_step: too large for one launch");
+    const dim3 grid((uint32_t)rg.bx, (uint32_t)nrows, (uint32_t)(npoly < 65535 ? npoly : 65535));
     auto k = wide ? (add ? lt_c0_kernel<2, true> : lt_c0_kernel<2, false>)
                   : (add ? lt_c0_kernel<1, true> : lt_c0_kernel<1, false>);
-    hipLaunchKernelGGL(k, grid, dim3(block), 0, st, (const void*)src, (void*)u, (uint64_t)src_stride,
+    hipLaunchKernelGGL(k, grid, dim3(rg.block), 0, st, (const void*)src, (void*)u, (uint64_t)src_stride,
                        (uint64_t)u_stride, ncoeff, (uint64_t)npoly, level, pmod, (const uint64_t*)c->d_dmod, galois_elt,
                        c->logN);
     MFHE_CHECK_LAUNCH("lt_c0_kernel");
@@ -230,21 +209,15 @@ static size_t lt_ws_words(size_t npoly, int beta, size_t rows, int level, size_t
 
 // The baby step of d_u (arguments checked, tables built): with a key, the gathered inner product into u and the c0
 // term added; without (g = 1), u = (P c0, P c1) on the Q rows and 0 on the special rows, x1 = c1.
-static int baby_body(mfhe_ctx* c, const uint64_t* d_c0, size_t in_stride, const uint64_t* x1, size_t digit_stride,
-                     size_t poly_stride, const uint64_t* d_gk, uint64_t* d_u, size_t u_stride, size_t npoly,
-                     const KsGeom& g, int beta, const uint64_t* pmod, uint32_t galois_elt, hipStream_t st) {
+static int baby_body(mfhe_ctx* c, const uint64_t* d_c0, size_t in_stride, const KsRaised& x1, const uint64_t* d_gk,
+                     uint64_t* d_u, size_t u_stride, size_t npoly, const KsGeom& g, int beta, const uint64_t* pmod,
+                     uint32_t galois_elt, hipStream_t st) {
     const size_t pw = (size_t)g.rows() * c->N;
-    int rc;
     if (!d_gk) {
-        if ((rc = launch_lt_c0(c, d_c0, in_stride, d_u, u_stride, npoly, g.level, g.rows(), pmod, 0, false, st)))
-            return rc;
-        return launch_lt_c0(c, x1, in_stride, d_u + pw, u_stride, npoly, g.level, g.rows(), pmod, 0, false, st);
+        RC(launch_lt_c0(c, d_c0, in_stride, d_u, u_stride, npoly, g.level, g.rows(), pmod, 0, false, st));
+        return launch_lt_c0(c, x1.p, in_stride, d_u + pw, u_stride, npoly, g.level, g.rows(), pmod, 0, false, st);
     }
-    KsipArgs a{};
-    a.raised = x1; a.ksk = d_gk; a.acc = d_u;
-    a.digit_stride = digit_stride; a.poly_stride = poly_stride; a.acc_stride = u_stride;
-    a.ncoeff = c->N; a.npoly = npoly; a.ndigits = beta; a.g = g; a.galois_elt = galois_elt;
-    if ((rc = launch_ksk_inner_product(c, a, st))) return rc;
+    RC(ks_inner_product(c, x1, d_gk, d_u, u_stride, npoly, beta, g, galois_elt, st));
     return launch_lt_c0(c, d_c0, in_stride, d_u, u_stride, npoly, g.level, g.level, pmod, galois_elt, true, st);
 }
 
@@ -252,21 +225,18 @@ static int baby_body(mfhe_ctx* c, const uint64_t* d_c0, size_t in_stride, const 
 
 using namespace mfhe;
 
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 extern "C" int mfhe_lt_baby_step(mfhe_ctx* c, const uint64_t* d_c0, size_t in_stride, const uint64_t* d_raised,
                                  size_t digit_stride, size_t poly_stride, const uint64_t* d_gk, uint64_t* d_u,
                                  size_t u_stride, size_t npoly, int level, int key_level, int alpha, int special_start,
                                  int nspecial, int galois_elt, mfhe_stream_t s) {
     RC(ks_check_ctx(c));
     if (!d_c0 || !d_raised || !d_u) return set_error(MFHE_EINVAL, "lt_baby_step: null pointer");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "lt_baby_step: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "lt_baby_step"));
+    RC(ks_check_digits(c, alpha, g, "lt_baby_step"));
     RC(ks_check_galois(c, galois_elt, "lt_baby_step"));
     if (!d_gk && galois_elt != 1) return set_error(MFHE_EINVAL, "lt_baby_step: null key for a Galois element other than 1");
     const size_t N = c->N, pw = (size_t)g.rows() * N, lw = (size_t)level * N;
-    const int beta = (level + alpha - 1) / alpha;
+    const int beta = ks_beta(level, alpha);
     if (in_stride < lw) return set_error(MFHE_EINVAL, "lt_baby_step: input poly stride smaller than level * N");
     if (u_stride / N < 2 * (size_t)g.rows()) return set_error(MFHE_EINVAL, "lt_baby_step: u poly stride smaller than 2 rows * N");
     const size_t isp = ks_span(npoly, in_stride, lw), usp = ks_span(npoly, u_stride, 2 * pw);
@@ -278,14 +248,14 @@ extern "C" int mfhe_lt_baby_step(mfhe_ctx* c, const uint64_t* d_c0, size_t in_st
             return set_error(MFHE_EINVAL, "lt_baby_step: digit stride smaller than the polynomials of a digit");
         rsp = ks_span(beta, digit_stride, dsp);
     }
-    if (ks_ranges_overlap(d_c0, isp, d_u, usp) || ks_ranges_overlap(d_raised, rsp, d_u, usp) ||
-        (d_gk && ks_ranges_overlap(d_gk, (size_t)beta * 2 * g.key_rows() * N, d_u, usp)))
-        return set_error(MFHE_EINVAL, "lt_baby_step: an input overlaps d_u");
+    RC(ks_check_overlap("lt_baby_step",
+                        {{d_c0, isp}, {d_raised, rsp}, {d_gk, d_gk ? (size_t)beta * 2 * g.key_rows() * N : 0}},
+                        {{d_u, usp}}));
     if (npoly == 0) return MFHE_OK;
     const uint64_t* pmod = nullptr;
     RC(ksk_pmod_table(c, key_level, special_start, nspecial, &pmod));
-    return baby_body(c, d_c0, in_stride, d_raised, digit_stride, poly_stride, d_gk, d_u, u_stride, npoly, g, beta, pmod,
-                     (uint32_t)galois_elt, (hipStream_t)s);
+    return baby_body(c, d_c0, in_stride, {d_raised, digit_stride, poly_stride}, d_gk, d_u, u_stride, npoly, g, beta,
+                     pmod, (uint32_t)galois_elt, (hipStream_t)s);
 }
 
 extern "C" int mfhe_lt_pt_mac(mfhe_ctx* c, const uint64_t* d_u, size_t slot_stride, size_t poly_stride, int nslots,
@@ -309,9 +279,8 @@ extern "C" int mfhe_lt_pt_mac(mfhe_ctx* c, const uint64_t* d_u, size_t slot_stri
     if (npoly && slot_stride < ssp) return set_error(MFHE_EINVAL, "lt_pt_mac: slot stride smaller than the polynomials of a slot");
     if (pt_stride < ptw) return set_error(MFHE_EINVAL, "lt_pt_mac: pt stride smaller than (pt_level + K) * N");
     const size_t asp = ks_span(npoly, acc_stride, 2 * pw);
-    if (ks_ranges_overlap(d_u, ks_span(nslots, slot_stride, ssp), d_acc, asp) ||
-        ks_ranges_overlap(d_pt, ks_span(npt, pt_stride, ptw), d_acc, asp))
-        return set_error(MFHE_EINVAL, "lt_pt_mac: an input overlaps d_acc");
+    RC(ks_check_overlap("lt_pt_mac", {{d_u, ks_span(nslots, slot_stride, ssp)}, {d_pt, ks_span(npt, pt_stride, ptw)}},
+                        {{d_acc, asp}}));
     LtMacArgs a{};
     a.u = d_u; a.pt = d_pt; a.acc = d_acc;
     a.slot_stride = slot_stride; a.poly_stride = poly_stride; a.pt_stride = pt_stride; a.acc_stride = acc_stride;
@@ -332,10 +301,8 @@ extern "C" int mfhe_lt_reserve(mfhe_ctx* c, size_t npoly, int level, int key_lev
     const KsGeom g{level, key_level, special_start, nspecial};
     RC(ks_check_geom(c, g, "lt_reserve"));
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    const uint64_t* pmod = nullptr;
-    RC(ksk_pmod_table(c, key_level, special_start, nspecial, &pmod));
-    return grow_ws(c, lt_ws_words(npoly, t.beta, (size_t)g.rows(), level, c->N, n_baby) * 8);
+    return ks_prepare(c, g, alpha, kKsPmod,
+                      lt_ws_words(npoly, ks_beta(level, alpha), (size_t)g.rows(), level, c->N, n_baby), t);
 }
 
 extern "C" int mfhe_lt_apply(mfhe_ctx* c, const mfhe_lt_plan* plan, const uint64_t* d_c0, const uint64_t* d_c1,
@@ -344,9 +311,8 @@ extern "C" int mfhe_lt_apply(mfhe_ctx* c, const mfhe_lt_plan* plan, const uint64
                              int special_start, int nspecial, mfhe_stream_t s) {
     RC(ks_check_ctx(c));
     if (!plan || !d_c0 || !d_c1 || !d_pt || !d_out0 || !d_out1) return set_error(MFHE_EINVAL, "lt_apply: null pointer");
-    if (alpha < 1) return set_error(MFHE_EINVAL, "lt_apply: alpha < 1");
     const KsGeom g{level, key_level, special_start, nspecial};
-    RC(ks_check_geom(c, g, "lt_apply"));
+    RC(ks_check_digits(c, alpha, g, "lt_apply"));
     if (pt_level < level) return set_error(MFHE_EINVAL, "lt_apply: pt_level < level");
     RC(ks_check_geom(c, KsGeom{level, pt_level, special_start, nspecial}, "lt_apply (plaintexts)"));
     std::vector<LtGroup> groups;
@@ -355,36 +321,26 @@ extern "C" int mfhe_lt_apply(mfhe_ctx* c, const mfhe_lt_plan* plan, const uint64
         return set_error(MFHE_EINVAL, std::string("lt_apply: ") + lt_plan_error_text(e));
     const size_t N = c->N, rows = (size_t)g.rows(), pw = rows * N, lw = (size_t)level * N;
     const size_t ptw = ((size_t)pt_level + nspecial) * N, kw = 2 * (size_t)g.key_rows() * N;
-    const int beta = (level + alpha - 1) / alpha;
+    const int beta = ks_beta(level, alpha);
     if (in_stride < lw || out_stride < lw) return set_error(MFHE_EINVAL, "lt_apply: poly stride smaller than level * N");
     if (pt_stride < ptw) return set_error(MFHE_EINVAL, "lt_apply: pt stride smaller than (pt_level + K) * N");
     const size_t isp = ks_span(npoly, in_stride, lw), osp = ks_span(npoly, out_stride, lw);
-    const size_t psp = ks_span(plan->nterms, pt_stride, ptw);
-    uint64_t* outs[2] = {d_out0, d_out1};
-    for (uint64_t* o : outs) {
-        if (ks_ranges_overlap(d_c0, isp, o, osp) || ks_ranges_overlap(d_c1, isp, o, osp) ||
-            ks_ranges_overlap(d_pt, psp, o, osp))
-            return set_error(MFHE_EINVAL, "lt_apply: an input overlaps an output");
-        for (int b = 1; b < plan->n_baby; ++b)
-            if (baby_used[b] && ks_ranges_overlap(plan->d_gk_baby[b], beta * kw, o, osp))
-                return set_error(MFHE_EINVAL, "lt_apply: a key overlaps an output");
-        for (const LtGroup& gr : groups)
-            if (gr.giant && ks_ranges_overlap(plan->d_gk_giant[gr.giant], beta * kw, o, osp))
-                return set_error(MFHE_EINVAL, "lt_apply: a key overlaps an output");
-    }
-    if (ks_ranges_overlap(d_out0, osp, d_out1, osp)) return set_error(MFHE_EINVAL, "lt_apply: the outputs overlap");
+    std::vector<KsRange> in{{d_c0, isp}, {d_c1, isp}, {d_pt, ks_span(plan->nterms, pt_stride, ptw)}};
+    for (int b = 1; b < plan->n_baby; ++b)   // and every key that is read
+        if (baby_used[b]) in.push_back({plan->d_gk_baby[b], beta * kw});
+    for (const LtGroup& gr : groups)
+        if (gr.giant) in.push_back({plan->d_gk_giant[gr.giant], beta * kw});
+    const KsRange out[2] = {{d_out0, osp}, {d_out1, osp}};
+    RC(ks_check_overlap("lt_apply", in.data(), in.size(), out, 2));
     if (npoly == 0) return MFHE_OK;
     // every table and the workspace before the first launch (nothing to do after mfhe_lt_reserve)
     KsTables t;
-    RC(ks_tables(c, g, alpha, t));
-    const uint64_t* pmod = nullptr;
-    RC(ksk_pmod_table(c, key_level, special_start, nspecial, &pmod));
-    RC(grow_ws(c, lt_ws_words(npoly, t.beta, rows, level, N, plan->n_baby) * 8));
+    RC(ks_prepare(c, g, alpha, kKsPmod, lt_ws_words(npoly, beta, rows, level, N, plan->n_baby), t));
     hipStream_t st = (hipStream_t)s;
-    uint64_t* raised = (uint64_t*)c->ws;                       // [beta][npoly][rows][N]     the key switch's block
-    uint64_t* acc = raised + (size_t)t.beta * npoly * pw;      // [npoly][2][rows][N]
-    uint64_t* scratch = acc + 2 * npoly * pw;                  // 2 npoly rows N words
-    uint64_t* U = scratch + 2 * npoly * pw;                    // [n_baby][npoly][2][rows][N]
+    const KsWs w = ks_ws(npoly, beta, rows, N);                // the key switch's block, then
+    const KsRaised raised = ks_ws_raised(c, npoly, g);
+    uint64_t* scratch = (uint64_t*)c->ws + w.scratch;
+    uint64_t* U = (uint64_t*)c->ws + w.end;                    // [n_baby][npoly][2][rows][N]
     uint64_t* A = U + (size_t)plan->n_baby * 2 * npoly * pw;   // [npoly][2][rows][N]
     uint64_t* w0 = A + 2 * npoly * pw;                         // [npoly][level][N]
     uint64_t* w1 = w0 + npoly * lw;                            // [npoly][level][N]
@@ -392,14 +348,14 @@ extern "C" int mfhe_lt_apply(mfhe_ctx* c, const mfhe_lt_plan* plan, const uint64
 
     bool keyed = false;
     for (int b = 1; b < plan->n_baby; ++b) keyed = keyed || baby_used[b];
-    if (keyed) RC(raise_body(c, d_c1, in_stride, raised, npoly * pw, pw, npoly, g, alpha, t, scratch, st));
+    if (keyed) RC(ks_raise_ws(c, d_c1, in_stride, npoly, g, alpha, t, st));
     for (int b = 0; b < plan->n_baby; ++b) {
         if (!baby_used[b]) continue;
         if (b == 0)
-            RC(baby_body(c, d_c0, in_stride, d_c1, 0, 0, nullptr, U, 2 * pw, npoly, g, t.beta, pmod, 1, st));
+            RC(baby_body(c, d_c0, in_stride, {d_c1, 0, 0}, nullptr, U, 2 * pw, npoly, g, beta, t.pmod, 1, st));
         else
-            RC(baby_body(c, d_c0, in_stride, raised, npoly * pw, pw, plan->d_gk_baby[b], U + (size_t)b * slot, 2 * pw,
-                         npoly, g, t.beta, pmod, (uint32_t)plan->baby_elt[b], st));
+            RC(baby_body(c, d_c0, in_stride, raised, plan->d_gk_baby[b], U + (size_t)b * slot, 2 * pw, npoly, g, beta,
+                         t.pmod, (uint32_t)plan->baby_elt[b], st));
     }
     bool started = false;   // `out` holds a partial sum
     for (const LtGroup& gr : groups) {
@@ -413,37 +369,22 @@ extern "C" int mfhe_lt_apply(mfhe_ctx* c, const mfhe_lt_plan* plan, const uint64
             m.term_pt[k] = gr.first + k;
         }
         RC(launch_lt_pt_mac(c, m, npoly, st));
-        // ModDown of both components as one batch of 2 npoly polynomials, then one tail per component
-        const uint64_t* cen = nullptr;
-        RC(ntt_moddown_center(c, A, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
         if (gr.giant == 0) {
-            for (int k = 0; k < 2; ++k)
-                RC(launch_sub_scale(c, A + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_stride,
-                                    started ? outs[k] : nullptr, npoly, level, nspecial, t.down, st));
+            RC(ks_moddown_pair(c, A, scratch, {d_out0, d_out1, out_stride, started ? 3 : 0}, npoly, g, t, st));
             started = true;
             continue;
         }
-        uint64_t* w[2] = {w0, w1};
-        for (int k = 0; k < 2; ++k)
-            RC(launch_sub_scale(c, A + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, w[k], lw, nullptr, npoly,
-                                level, nspecial, t.down, st));
+        RC(ks_moddown_pair(c, A, scratch, {w0, w1, lw, 0}, npoly, g, t, st));
         // the rotation of (w0, w1), added into out: out0 (+)= sigma(w0), then the key switch of sigma(w1) with out as
         // the addend of ModDown's tails
         const uint32_t ge = (uint32_t)plan->giant_elt[gr.giant];
-        RC(raise_body(c, w1, lw, raised, npoly * pw, pw, npoly, g, alpha, t, scratch, st));
+        RC(ks_raise_ws(c, w1, lw, npoly, g, alpha, t, st));
         if (started)
             RC(launch_lt_c0(c, w0, lw, d_out0, out_stride, npoly, level, level, nullptr, ge, true, st));
         else
             RC(launch_automorphism(c, w0, lw, d_out0, out_stride, npoly, level, ge, st));
-        KsipArgs a{};
-        a.raised = raised; a.ksk = plan->d_gk_giant[gr.giant]; a.acc = acc;
-        a.digit_stride = npoly * pw; a.poly_stride = pw; a.acc_stride = 2 * pw;
-        a.ncoeff = N; a.npoly = npoly; a.ndigits = t.beta; a.g = g; a.galois_elt = ge;
-        RC(launch_ksk_inner_product(c, a, st));
-        RC(ntt_moddown_center(c, acc, pw, 2 * npoly, level, special_start, nspecial, t.down, scratch, &cen, st));
-        for (int k = 0; k < 2; ++k)
-            RC(launch_sub_scale(c, acc + (size_t)k * pw, 2 * pw, cen + (size_t)k * lw, 2 * lw, outs[k], out_stride,
-                                (k == 0 || started) ? outs[k] : nullptr, npoly, level, nspecial, t.down, st));
+        RC(ks_apply_raised(c, raised, plan->d_gk_giant[gr.giant], {d_out0, d_out1, out_stride, started ? 3 : 1}, npoly,
+                           g, t, ge, st));
         started = true;
     }
     return MFHE_OK;

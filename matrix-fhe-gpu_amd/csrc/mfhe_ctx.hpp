@@ -41,6 +41,9 @@ int ensure_xy(mfhe_ctx* c);   // XY encoder matrices, built on first use (ctx.cp
         if (_e != hipSuccess) return ::mfhe::hip_error(_e, what); \
     } while (0)
 
+// return the MFHE_* code of a failed internal call (its error text is already set)
+#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
+
 // Per-limb constants of the FP64 wide-CRT fast path (crt.hip compose_fast): one 64-B scalar load per limb.
 struct CrtLimbF {
     uint64_t q;

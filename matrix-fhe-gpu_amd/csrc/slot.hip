@@ -381,8 +381,6 @@ static uint64_t invmod(uint64_t x, uint64_t q) {
 using namespace mfhe;
 using namespace mfhe::slot;
 
-#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 extern "C" int mfhe_slot_reserve(mfhe_ctx* c, size_t npoly, int level, int special_start, int nspecial) {
     RC(check_ctx(c));
     RC(check_rows(c, level, special_start, nspecial, "slot_reserve"));

@@ -31,7 +31,7 @@ U64_BITS, F64_BITS = (50, 61), (45, 49)
 # 1. inner product: runs longer than kKsipMinRun
 # ---------------------------------------------------------------------------------------------------------------
 def _prun(npoly, bx, rows):
-    """launch_ksk_inner_product's rule (csrc/keyswitch.hip): runs = max(1, 4096 / (bx rows)) workgroup columns,
+    """launch_ksk_inner_product's rule (ks_runs, csrc/ks_host.hpp): runs = max(1, 4096 / (bx rows)) workgroup columns,
     prun = ceil(npoly / runs), but never below kKsipMinRun = 4 (or the batch, when that is smaller)."""
     runs = max(1, 4096 // (bx * rows))
     prun = -(-npoly // runs)
@@ -101,7 +101,7 @@ AUTO_CASES = [(3, 21845), (3, 21846), (1, 65536 + 7)]
 def test_automorphism_beyond_65535_rows(mfhe, log_n, rows, npoly):
     import torch
     (ctx, mod), n = _ctx3(log_n), 1 << log_n
-    # launch_automorphism's fold (csrc/galois.hip): gy = min(total, 65535), gz = ceil(total / gy)
+    # launch_automorphism's fold (ks_fold, csrc/ks_host.hpp): gy = min(total, 65535), gz = ceil(total / gy)
     total = npoly * rows
     gy = min(total, 65535)
     assert -(-total // gy) == (1 if npoly == 21845 else 2)
