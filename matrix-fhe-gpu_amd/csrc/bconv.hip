@@ -318,16 +318,6 @@ static int check_moddown(const mfhe_ctx* c, int keep, int drop_start, int drop_c
     return check_range(c, drop_start, drop_count, "moddown");
 }
 
-int grow_ws(mfhe_ctx* c, size_t need) {
-    if (c->ws_bytes >= need) return MFHE_OK;
-    if (c->ws) MFHE_HIP(hipFree(c->ws));
-    c->ws = nullptr;
-    c->ws_bytes = 0;
-    MFHE_HIP(hipMalloc(&c->ws, need));
-    c->ws_bytes = need;
-    return MFHE_OK;
-}
-
 // ---- NTT-domain bodies with the scratch base as an argument (the public calls pass the context workspace; the key
 // switch passes a part of its own block) ----
 int ntt_modup_tables(mfhe_ctx* c, int digit_start, int digit_count, const ModUpPlan& pl, const uint64_t* tab[3]) {

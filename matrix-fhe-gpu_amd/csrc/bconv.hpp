@@ -45,8 +45,6 @@ int launch_bconv(BconvArgs a, size_t npoly, int kernel_mode, hipStream_t st);
 // One launch: dst[p][w] = src[p][w] for w < words, the npoly blocks src_stride / dst_stride words apart.
 int launch_copy_rows(const uint64_t* src, size_t src_stride, uint64_t* dst, size_t dst_stride, size_t npoly,
                      size_t words, hipStream_t st);
-// Grow the context workspace to `need` bytes (frees and reallocates; nothing when it is large enough).
-int grow_ws(mfhe_ctx* c, size_t need);
 
 // The destination ranges of a ModUp of digit [ds, ds + dc) at `level`: below the digit, above it, the special limbs
 // (the non-empty ones), each with its first context limb, its first output row and its count.

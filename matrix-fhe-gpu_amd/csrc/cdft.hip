@@ -344,7 +344,7 @@ int launch_cwdft_inv_dots(const CGemmArgs& a, const double2* in, const double2* 
 }
 
 // ---- the per-lane XY product out = A M B in one launch (r06, n = 64) ----
-// he.hip xy3 at n = 64: A and B the shared 64 x 64 encoder matrices, M one lane's 64 x 64 block; one workgroup per
+// wtrans.hip xy3 at n = 64: A and B the shared 64 x 64 encoder matrices, M one lane's 64 x 64 block; one workgroup per
 // lane, eight waves of 16 x 32 outputs.  Phase 1 is cgemm_mfma_kernel<0>'s T = A M (v_mfma_f64_16x16x4_f64 blocks,
 // each output accumulated in the same order, k-step by k-step: first the Ar Br / Ar Bi terms, then -Ai Bi / Ai Br),
 // with all of K in LDS at once; T then goes to LDS instead of HBM and phase 2 is out = T B the same way.  So the

@@ -44,7 +44,7 @@ int launch_wdft_rader(const double2* in, double2* out, uint32_t Pf, const double
 int launch_wdft_rader_inv(const double2* in, double2* out, double* out_im, uint32_t Pf, const double2* rb,
                           const int16_t* gp, const double2* lam, const int8_t* phi, hipStream_t s);
 // out = A M B per lane for 64 x 64 complex blocks (A, B shared; M, out [lanes][64][64]) in one launch: the two
-// launch_cgemm products of he.hip xy3 without the intermediate's HBM round trip, the same doubles (cdft.hip)
+// launch_cgemm products of wtrans.hip xy3 without the intermediate's HBM round trip, the same doubles (cdft.hip)
 int launch_xy_fused(const double2* A, const double2* M, const double2* B, double2* out, int lanes, hipStream_t s);
 // the same products at n = 64 by 64-point FFTs (V = ensure_xy's encoder matrix; inv: V^-1 M V^-T), equal to
 // rounding; in and out must not overlap (cdft.hip xy_fft_kernel takes both as __restrict__)

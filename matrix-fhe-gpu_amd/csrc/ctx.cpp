@@ -34,6 +34,18 @@ int hip_error(hipError_t e, const char* what) {
     return set_error(MFHE_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+int grow_dev(void*& p, size_t& bytes, size_t need) {
+    if (bytes >= need) return MFHE_OK;
+    if (p) MFHE_HIP(hipFree(p));
+    p = nullptr;
+    bytes = 0;
+    MFHE_HIP(hipMalloc(&p, need));
+    bytes = need;
+    return MFHE_OK;
+}
+
+int grow_ws(mfhe_ctx* c, size_t need) { return grow_dev(c->ws, c->ws_bytes, need); }
+
 template <class T>
 static int dalloc(mfhe_ctx* c, T** p, size_t n) {
     void* ptr = nullptr;

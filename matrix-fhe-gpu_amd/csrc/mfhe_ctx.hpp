@@ -28,6 +28,13 @@ int comm_size_rank(const mfhe_comm* comm, int* size, int* rank);
 int comm_agree(mfhe_comm* comm, int local_rc, hipStream_t s);
 int hip_error(hipError_t e, const char* what);
 int ensure_xy(mfhe_ctx* c);   // XY encoder matrices, built on first use (ctx.cpp)
+// ctx.cpp: a device buffer that only grows: nothing when bytes >= need, else free, allocate `need`, record.  On a
+// failed allocation the buffer is left empty (p null, bytes 0).
+int grow_dev(void*& p, size_t& bytes, size_t need);
+int grow_ws(mfhe_ctx* c, size_t need);   // grow_dev of the context's pipeline workspace (ws, ws_bytes)
+// crt.hip: two composes of the same shape (a -> oa, b -> ob) in one launch
+int crt_compose_f64_pair(mfhe_ctx* c, const uint64_t* a, const uint64_t* b, size_t npoly, size_t ncoeff, double* oa,
+                         double* ob, size_t stride, hipStream_t s);
 
 #define MFHE_HIP(call)                                          \
     do {                                                        \

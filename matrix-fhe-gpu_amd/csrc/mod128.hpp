@@ -1,5 +1,8 @@
-// mod128.hpp -- device modular reductions shared by the RNS kernels (bconv.hip, keyswitch.hip): a Shoup multiply
-// and the 128-bit Barrett reduction against the DModulus constants of d_dmod.
+// mod128.hpp -- device modular reductions, one definition each:
+//   shoup_mul, barrett128 (against the DModulus constants of d_dmod) and Lane: the RNS kernels (bconv.hip,
+//     keyswitch.hip, galois.hip, lintrans.hip, ctmul.hip, ctmat.hip, slot.hip)
+//   mod_u128_fold (against d_rns_mu and d_r64): he.hip mul_s_kernel and ct_mul_kernel, wcrt_gemm.hip mod_gemm_kernel,
+//     trace.hip's u128 kernel
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +26,24 @@ __device__ __forceinline__ uint64_t barrett128(u128 x, uint64_t q, uint64_t r0, 
     const uint64_t qhat = x1 * r1 + (uint64_t)(a >> 64) + (uint64_t)(b >> 64);
     const uint64_t r = x0 - qhat * q;
     return r >= q ? r - q : r;
+}
+
+// (hi:lo) mod q for q < 2^63: fold hi down with r64 = 2^64 mod q until it is zero (each round's value is congruent and
+// smaller), then one Barrett step with mu = floor(2^64 / q).  For lo < 2^64, lo / q - lo mu / 2^64 < lo / 2^64 < 1,
+// so the quotient estimate floor(lo mu / 2^64) is at most one low and r < 2q: one select canonicalises.
+__device__ __forceinline__ uint64_t mod_u128_fold(uint64_t hi, uint64_t lo, uint64_t q, uint64_t mu, uint64_t r64) {
+    while (hi) {
+        const u128 t = (u128)hi * r64 + lo;
+        hi = (uint64_t)(t >> 64);
+        lo = (uint64_t)t;
+    }
+    const uint64_t r = lo - __umul64hi(lo, mu) * q;
+    return r >= q ? r - q : r;
+}
+// a b mod q for any 64-bit a, b
+__device__ __forceinline__ uint64_t mulmod_fold(uint64_t a, uint64_t b, uint64_t q, uint64_t mu, uint64_t r64) {
+    const u128 v = (u128)a * b;
+    return mod_u128_fold((uint64_t)(v >> 64), (uint64_t)v, q, mu, r64);
 }
 
 // V coefficients per thread: one u64, or two with a 16-byte load / store

@@ -13,6 +13,14 @@
 
 namespace mfhe {
 
+// matrix-major [w][l][y][x] index i -> poly-major [w n + y][l][x] (HE.cu:1330-1368)
+__device__ __forceinline__ uint64_t pm_index(uint64_t i, int log_n, int L) {
+    const uint64_t n = 1ull << log_n;
+    const uint64_t x = i & (n - 1), y = (i >> log_n) & (n - 1);
+    const uint32_t wl = (uint32_t)(i >> (2 * log_n)), w = wl / (uint32_t)L, l = wl - w * (uint32_t)L;   // wl < 2^32
+    return (((uint64_t)w * n + y) * L + l) * n + x;
+}
+
 // ---------------- fused X-axis ring product (n = 4..64) ----------------
 // t = INTT(NTT(a) (.) s) for one length-n row, phantom convention (the ph tables of mfhe_ntt_fwd/_inv, so
 // s = mfhe_ntt_fwd(secret) is in the matching order): the reference's xy_ntt_forward_phantom ->

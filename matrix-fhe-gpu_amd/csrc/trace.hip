@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "mfhe_ctx.hpp"
+#include "mod128.hpp"
 
 namespace mfhe {
 
@@ -25,19 +26,6 @@ namespace {
 constexpr int TR_TILE = 64;   // output tile edge
 constexpr int TR_KP = 16;     // k-panel depth staged in LDS
 constexpr int TR_LDS = 68;    // padded row stride (doubles): 2-way conflicts on the transposing store
-
-// (hi:lo) mod q: fold hi with r64 = 2^64 mod q, then Barrett with mu = floor(2^64 / q)
-__device__ __forceinline__ uint64_t tr_mod128(unsigned __int128 v, uint64_t q, uint64_t mu, uint64_t r64) {
-    uint64_t hi = (uint64_t)(v >> 64), lo = (uint64_t)v;
-    while (hi) {
-        const unsigned __int128 t = (unsigned __int128)hi * r64 + lo;
-        hi = (uint64_t)(t >> 64);
-        lo = (uint64_t)t;
-    }
-    uint64_t r = lo - __umul64hi(lo, mu) * q;
-    r = r >= q ? r - q : r;
-    return r >= q ? r - q : r;
-}
 
 // map_Bprime_batched_kernel (batched_trace.cu:37-79): conj(B), row j -> (n - j) mod n, rows j != 0 times -i.
 
@@ -417,13 +405,12 @@ __global__ void trace_gemm_u128_kernel(const uint64_t* __restrict__ Ar, const ui
     const uint64_t row = pos >> log_n, col = pos & (n - 1), base = mat << (2 * log_n);
     const int l = (int)(mat % (uint64_t)L);
     const uint64_t q = qmu[2 * l], mu = qmu[2 * l + 1], rr = r64[l];
-    using u128 = unsigned __int128;
     uint64_t acc_r = 0, acc_i = 0;
     for (int t = 0; t < n; ++t) {
         const uint64_t ar = Ar[base + row * n + t], ai = Ai[base + row * n + t];
         const uint64_t br = Br[base + col * n + t], bi = Bi[base + col * n + t];
-        const uint64_t rrp = tr_mod128((u128)ar * br, q, mu, rr), iip = tr_mod128((u128)ai * bi, q, mu, rr);
-        const uint64_t rip = tr_mod128((u128)ar * bi, q, mu, rr), irp = tr_mod128((u128)ai * br, q, mu, rr);
+        const uint64_t rrp = mulmod_fold(ar, br, q, mu, rr), iip = mulmod_fold(ai, bi, q, mu, rr);
+        const uint64_t rip = mulmod_fold(ar, bi, q, mu, rr), irp = mulmod_fold(ai, br, q, mu, rr);
         const uint64_t pr = rrp >= iip ? rrp - iip : q - (iip - rrp);
         uint64_t pi = rip + irp;
         pi = pi >= q ? pi - q : pi;
@@ -433,8 +420,8 @@ __global__ void trace_gemm_u128_kernel(const uint64_t* __restrict__ Ar, const ui
         acc_i = s >= q ? s - q : s;
     }
     const uint64_t nm = (uint64_t)n % q;
-    Cr[idx] = tr_mod128((u128)acc_r * nm, q, mu, rr);
-    Ci[idx] = tr_mod128((u128)acc_i * nm, q, mu, rr);
+    Cr[idx] = mulmod_fold(acc_r, nm, q, mu, rr);
+    Ci[idx] = mulmod_fold(acc_i, nm, q, mu, rr);
 }
 
 struct RescaleArgs {

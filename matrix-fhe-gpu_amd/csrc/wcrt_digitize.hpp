@@ -2,6 +2,7 @@
 // dense, factored forward (four sources, pair form), factored inverse, and the inverse with the decrypt fused in
 // front (single and pair, with the column-sum kernels of a split launch).  Included by wcrt_gemm.hip only.
 #pragma once
+#include "he_sample.hpp"
 #include "mfhe_ctx.hpp"
 #include "ring_row.hpp"
 #include "wcrt_gemm.hpp"
@@ -201,24 +202,21 @@ __global__ __launch_bounds__(256, 4) void mfma_digitize_fold_kernel(const uint64
         uq = fs.qmu[2 * l];
         umu = fs.qmu[2 * l + 1];
     }
-    // SRC 2: the sampler's LCG output for row r, (123456789 + ((r Ltot + lbase + l) << 2 log n) + p) A + C mod 2^64
-    // (he.hip uniform_kernel).  It is affine in r: with the per-row step K = (Ltot << 2 log n) A, row r + 1's word is
-    // row r's + K, and row r + 257's is row r's + 257 K -- 64-bit adds in the row loop instead of a 64-bit multiply
-    // per value, the same words (sampled_row below; in(r) keeps the direct form for the d0 rows).
+    // SRC 2: the sampler's word for row r (he_sample.hpp uniform_seed, as he.hip uniform_kernel draws it).  It is affine
+    // in r: with the per-row step K = (Ltot << 2 log n) A, row r + 1's word is row r's + K, and row r + 257's is row
+    // r's + 257 K -- 64-bit adds in the row loop instead of a 64-bit multiply per value, the same words (in(r) keeps
+    // the direct form for the d0 rows).
     uint64_t lcgK = 0, lcgK257 = 0;
     if constexpr (SRC == 2) {
-        lcgK = ((uint64_t)fs.Ltot << (2 * log_n)) * 6364136223846793005ULL;
+        lcgK = ((uint64_t)fs.Ltot << (2 * log_n)) * kUniformLcgA;
         lcgK257 = lcgK * 257ull;
     }
     auto lcg_seed = [&](int r) {
         const uint32_t pp = live ? p : 0;
-        return (123456789ULL + (((uint64_t)r * (uint64_t)fs.Ltot + (uint64_t)(fs.lbase + l)) << (2 * log_n)) + pp) *
-                   6364136223846793005ULL + 1442695040888963407ULL;
+        return uniform_seed((uint64_t)r, (uint64_t)(fs.lbase + l), (uint64_t)fs.Ltot, log_n, pp);
     };
-    auto sampled = [&](uint64_t seed) {   // Barrett as uniform_kernel: [0, 3q), then two selects
-        uint64_t v = seed - __umul64hi(seed, umu) * uq;
-        v = v >= uq ? v - uq : v;
-        v = v >= uq ? v - uq : v;
+    auto sampled = [&](uint64_t seed) {
+        const uint64_t v = uniform_reduce(seed, uq, umu);   // outside the select: dead lanes take no branch round it
         return live ? ArithF64::from_u64(v) : 0.0;
     };
     auto in = [&](int r) {

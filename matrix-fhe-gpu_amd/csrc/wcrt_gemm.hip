@@ -7,23 +7,11 @@
 
 #include "gemm_tile.hpp"
 #include "mfhe_ctx.hpp"
+#include "mod128.hpp"
 #include "wcrt_digitize.hpp"
 #include "wcrt_mfma.hpp"
 
 namespace mfhe {
-
-using u128 = unsigned __int128;
-
-// (hi:lo) mod q by folding hi with r64 = 2^64 mod q, then one Barrett step.
-__device__ __forceinline__ uint64_t mod_u128(uint64_t hi, uint64_t lo, uint64_t q, uint64_t mu, uint64_t r64) {
-    while (hi) {
-        const u128 t = (u128)hi * r64 + lo;
-        hi = (uint64_t)(t >> 64);
-        lo = (uint64_t)t;
-    }
-    uint64_t r = lo - __umul64hi(lo, mu) * q;
-    return r >= q ? r - q : r;
-}
 
 __global__ __launch_bounds__(NTH) void mod_gemm_kernel(ModGemmArgs a) {
     __shared__ uint64_t As[TM][TK + 1];
@@ -84,7 +72,7 @@ __global__ __launch_bounds__(NTH) void mod_gemm_kernel(ModGemmArgs a) {
         for (int j = 0; j < 4; ++j) {
             const uint32_t p = p0 + tx + 16 * j;
             if (p >= a.P) continue;
-            C[b_off(m, p, a.scM, a.scY, a.log_n)] = mod_u128(acc_hi[i][j], acc_lo[i][j], q, mu, r64);
+            C[b_off(m, p, a.scM, a.scY, a.log_n)] = mod_u128_fold(acc_hi[i][j], acc_lo[i][j], q, mu, r64);
         }
     }
 }

@@ -831,3 +831,116 @@ def test_he_wrappers_reject_undersized_buffers(mfhe, small):
     # the exact sizes pass
     ctx.matrix_to_poly(big[:W], big[W:])
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("n,L,shard", [(4, 2, None), (8, 11, None), (4, 2, (2, 5))])
+def test_encrypt_samplers_digitize_matches_kernels(mfhe, n, L, shard):
+    """encrypt_pair draws a and e inside the factored W-CRT's digitize (MFHE_OPT_WCRT_MFMA 1, default:
+    wcrt_digitize.hpp mfma_digitize_fold_kernel<D, 2> and gaussian_compact_kernel / gaussian_i8_kernel) or by
+    uniform_kernel and gaussian_kernel in front of the VALU GEMM (0): the same draws (he_sample.hpp), so the same
+    ciphertexts.  shard = (limb_base, limbs_total): the context holds limbs [limb_base, limb_base + L) of a larger
+    set, and the uniform seed depends on both."""
+    import torch
+    moduli = RNS[:L] if shard is None else RNS[shard[0]:shard[0] + L]
+    ctx = mfhe.Context(moduli, n.bit_length() - 1, CONV)
+    if shard is not None:
+        ctx.set_limb_shard(*shard)
+    words = 512 * L * n * n
+    rng = np.random.default_rng(n * 13 + L)
+    qm = np.array(moduli, np.uint64)[None, :, None]
+    m_re, m_im = (_dev(mfhe, (rng.integers(0, 2 ** 63, (512, L, n * n), dtype=np.uint64) % qm).ravel())
+                  for _ in range(2))
+    sk = torch.empty(512 * L * n, dtype=torch.int64, device="cuda")
+    ctx.keygen(sk)
+    out = {}
+    for mf in (1, 0):
+        ctx.set_option(mfhe.OPT_WCRT_MFMA, mf)
+        cre = torch.full((2 * words,), -1, dtype=torch.int64, device="cuda")
+        cim = torch.full_like(cre, -1)
+        ctx.encrypt_pair(m_re, m_im, sk, cre, cim)
+        torch.cuda.synchronize()
+        out[mf] = (mfhe.to_host_u64(cre), mfhe.to_host_u64(cim))
+    np.testing.assert_array_equal(out[1][0], out[0][0])
+    np.testing.assert_array_equal(out[1][1], out[0][1])
+    ctx.close()
+
+
+def _wide_moduli():
+    """Two W-CRT-capable primes (q = 1 mod 2^8 * 771) just under 2^59, the context's limit: products of two
+    residues fill 118 bits, and the 512-term W-CRT accumulators 127."""
+    from bench import gen_moduli
+    moduli = gen_moduli(59, 197376, 2)
+    assert all((1 << 58) < q < (1 << 59) for q in moduli)
+    return moduli
+
+
+def _wide_operands(rng, shape, qcol, kind):
+    """[...] residues mod qcol (broadcast): every one q - 1, or random."""
+    if kind == "max":
+        return np.broadcast_to(qcol - np.uint64(1), shape).copy()
+    return rng.integers(0, 2 ** 63, shape, dtype=np.uint64) % qcol
+
+
+@pytest.mark.parametrize("kind", ["max", "random"])
+def test_u128_fold_users_at_59_bit_moduli(mfhe, orc, kind):
+    """mod128.hpp mod_u128_fold at the largest moduli a W-CRT context takes, operands all q - 1 and random, against
+    Python integers, through three of its users at n = 4, L = 2: ct_mul_kernel (ct_mul_tensor), the VALU
+    mod_gemm_kernel (wcrt_fwd with MFHE_OPT_WCRT_MFMA 0) and mul_s_kernel (decrypt_to_eval with MFHE_OPT_HE_FUSED 0;
+    q >= 2^50 turns its FP64 branch off).  The fourth, trace.hip's u128 kernel, is in test_trace.py."""
+    import ctypes
+    import torch
+    n, L, n2 = 4, 2, 16
+    moduli = _wide_moduli()
+    ctx = mfhe.Context(moduli, 2, CONV)
+    rng = np.random.default_rng(59)
+    q3 = np.array(moduli, np.uint64)[None, :, None]
+    O = lambda a: a.astype(object)   # noqa: E731
+    words = 512 * L * n2
+    qo = O(np.broadcast_to(q3, (512, L, n2)))
+
+    # ct_mul_tensor: d0 = b1 b2, d1 = b1 a2 + a1 b2, d2 = a1 a2 over [b | a]
+    b1, a1, b2, a2 = (_wide_operands(rng, (512, L, n2), q3, kind) for _ in range(4))
+    d = [torch.empty(words, dtype=torch.int64, device="cuda") for _ in range(3)]
+    ctx.ct_mul_tensor(_dev(mfhe, np.concatenate([b1.ravel(), a1.ravel()])),
+                      _dev(mfhe, np.concatenate([b2.ravel(), a2.ravel()])), *d)
+    torch.cuda.synchronize()
+    want = [(O(b1) * O(b2)) % qo, (O(b1) * O(a2) + O(a1) * O(b2)) % qo, (O(a1) * O(a2)) % qo]
+    for got, w in zip(d, want):
+        np.testing.assert_array_equal(mfhe.to_host_u64(got).reshape(512, L, n2), w.astype(np.uint64))
+
+    # VALU W-CRT forward: out[w n + y][l][x] = sum_r V_l[w][r] in[r][l][y n + x] mod q, V the oracle's table (the
+    # context's own is the same construction: test_wcrt_mfma_matches_valu_and_oracle)
+    h = orc.HE(n, moduli, 2.0 ** 35)
+    V = np.ctypeslib.as_array(ctypes.cast(orc.L.orc_he_V(h.h), ctypes.POINTER(ctypes.c_uint64)), shape=(L, 512, 512))
+    x = _wide_operands(rng, (512, L, n2), q3, kind)
+    ctx.set_option(mfhe.OPT_WCRT_MFMA, 0)
+    f = torch.empty(words, dtype=torch.int64, device="cuda")
+    ctx.wcrt_fwd(_dev(mfhe, x.ravel()), f)
+    torch.cuda.synchronize()
+    got = mfhe.to_host_u64(f).reshape(512, n, L, n)
+    for l in range(L):
+        w = O(V[l]).dot(O(x[:, l, :])) % int(moduli[l])   # [w][y n + x]
+        np.testing.assert_array_equal(got[:, :, l, :], w.astype(np.uint64).reshape(512, n, n))
+
+    # unfused decrypt: out[w n + y][l][.] = b + a * s over X.  a = the constant c per row, so NTT(a) = c at every
+    # point and mul_s_kernel multiplies c by each word of s; s = NTT(s_coef) by the oracle, so a * s = c s_coef
+    ctx.set_option(mfhe.OPT_HE_FUSED, 0)
+    c = _wide_operands(rng, (512, L, n, 1), q3[..., None], kind)
+    b = _wide_operands(rng, (512, L, n, n), q3[..., None], kind)
+    if kind == "max":   # s = q - 1 at every point: s_coef = the constant q - 1
+        s_coef = np.zeros((512, L, n), np.uint64)
+        s_coef[:, :, 0] = np.array(moduli, np.uint64) - np.uint64(1)
+    else:
+        s_coef = _wide_operands(rng, (512, L, n), q3, kind)
+    s_ntt = orc.phantom_fwd(s_coef.ravel(), L, 2, moduli)
+    if kind == "max":
+        np.testing.assert_array_equal(s_ntt.reshape(512, L, n), np.broadcast_to(q3 - np.uint64(1), (512, L, n)))
+    a = np.zeros((512, L, n, n), np.uint64)
+    a[..., :1] = c
+    ev = torch.empty(words, dtype=torch.int64, device="cuda")
+    ctx.decrypt_to_eval(_dev(mfhe, np.concatenate([b.ravel(), a.ravel()])), _dev(mfhe, s_ntt), ev)
+    torch.cuda.synchronize()
+    want = (O(b) + O(c) * O(s_coef)[:, :, None, :]) % O(np.broadcast_to(q3[..., None], (512, L, n, n)))
+    np.testing.assert_array_equal(mfhe.to_host_u64(ev).reshape(512, n, L, n),
+                                  want.astype(np.uint64).transpose(0, 2, 1, 3))
+    ctx.close()

@@ -127,6 +127,33 @@ def test_trace_wide_moduli_vs_oracle(mfhe, orc, bits, split):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["max", "random"])
+def test_trace_u128_kernel_at_59_bit_moduli(mfhe, kind):
+    """The u128 kernel's reduction (mod128.hpp mod_u128_fold) at W-CRT-capable primes just under 2^59, the largest a
+    W-CRT context takes, at the smallest n: every operand q - 1, and random ones, against Python integers."""
+    import torch
+    from bench import gen_moduli
+    n, L, batch = 2, 2, 3
+    moduli = gen_moduli(59, 197376, L)
+    ctx = mfhe.Context(moduli, 6, mfhe.CONV_PHANTOM)
+    rng = np.random.default_rng(59)
+    if kind == "max":
+        q = np.array(moduli, np.uint64)[None, :, None]
+        ops = [np.broadcast_to(q - np.uint64(1), (batch, L, n * n)).ravel().copy() for _ in range(4)]
+    else:
+        ops = [_rand(rng, batch, L, n, moduli) for _ in range(4)]
+    d = [mfhe.to_device_u64(x) for x in ops]
+    bp = [torch.empty_like(d[0]), torch.empty_like(d[0])]
+    c = [torch.empty_like(d[0]), torch.empty_like(d[0])]
+    ctx.trace_map_bprime(d[2], d[3], bp[0], bp[1], n, L, batch)
+    ctx.trace_gemm(d[0], d[1], bp[0], bp[1], c[0], c[1], n, L, batch)
+    torch.cuda.synchronize()
+    er, ei = _py_trace(*ops, n, L, batch, moduli)
+    np.testing.assert_array_equal(mfhe.to_host_u64(c[0]), er)
+    np.testing.assert_array_equal(mfhe.to_host_u64(c[1]), ei)
+
+
+@pytest.mark.gpu
 def test_trace_invalid_arguments(mfhe):
     import torch
     ctx = mfhe.Context(RNS, 6, mfhe.CONV_PHANTOM)

@@ -7,6 +7,11 @@ data, so the operands are random residues.
   rocprofv3 --kernel-trace -d DIR -o run --output-format csv -- python tools/ks_launch_trace.py run
   python tools/ks_launch_trace.py list DIR > profiles/ks_launch_trace_<build>.txt
 
+The `he` scenario does the same for the pipelines of he.hip: one call each of keygen, encode, encrypt_pair,
+decrypt_to_eval and decrypt_and_decode at n = 8, L = 3 (the first three reference moduli), under the default options
+and again with MFHE_OPT_HE_STREAMS 0, HE_STREAMS 2, HE_FUSED 0 and WCRT_MFMA 0 (run `he` in place of `run`;
+profiles/he_launch_trace_<build>.txt).
+
 `list` prints the tool's name and then one line per dispatch, in dispatch order: kernel name, grid and workgroup size
 in threads.  Two builds launch alike when their lists are equal."""
 import csv
@@ -55,6 +60,34 @@ def run():
     torch.cuda.synchronize()
 
 
+def run_he():
+    sys.path.insert(0, str(ROOT / "matrix-fhe-gpu_amd"))
+    import torch
+    import mfhe
+
+    log_n, L = 3, 3
+    n2 = 1 << (2 * log_n)
+    words = 512 * L * n2
+    ctx = mfhe.Context(mfhe.RNS_MODULI[:L], log_n, mfhe.CONV_PHANTOM | mfhe.CONV_WCRT)
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    msg = torch.rand(2 * 512 * n2, generator=gen, device="cuda", dtype=torch.float64)
+    sk = torch.empty(512 * L << log_n, dtype=torch.int64, device="cuda")
+    re, im, ev = (torch.empty(words, dtype=torch.int64, device="cuda") for _ in range(3))
+    cre, cim = (torch.empty(2 * words, dtype=torch.int64, device="cuda") for _ in range(2))
+    out = torch.empty_like(msg)
+    defaults = {o: ctx.get_option(o) for o in (mfhe.OPT_HE_STREAMS, mfhe.OPT_HE_FUSED, mfhe.OPT_WCRT_MFMA)}
+    for opt, value in ((None, None), (mfhe.OPT_HE_STREAMS, 0), (mfhe.OPT_HE_STREAMS, 2), (mfhe.OPT_HE_FUSED, 0),
+                       (mfhe.OPT_WCRT_MFMA, 0)):
+        for o, v in defaults.items():
+            ctx.set_option(o, value if o == opt else v)
+        ctx.keygen(sk)
+        ctx.encode(msg, re, im)
+        ctx.encrypt_pair(re, im, sk, cre, cim)
+        ctx.decrypt_to_eval(cre, sk, ev)
+        ctx.decrypt_and_decode(cre, cim, sk, out)
+        torch.cuda.synchronize()
+
+
 def listing(d):
     files = sorted(Path(d).rglob("*kernel_trace.csv"))
     if len(files) != 1:
@@ -70,6 +103,8 @@ def listing(d):
 if __name__ == "__main__":
     if len(sys.argv) == 2 and sys.argv[1] == "run":
         run()
+    elif len(sys.argv) == 2 and sys.argv[1] == "he":
+        run_he()
     elif len(sys.argv) == 3 and sys.argv[1] == "list":
         listing(sys.argv[2])
     else:
