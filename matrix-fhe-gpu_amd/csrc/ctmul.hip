@@ -207,6 +207,12 @@ int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, ui
     RC(ks_switch_body(c, ctmul_d2(c, npoly, t.beta, g), lw, d_rlk, {d_out0, d_out1, out_poly_stride, 3}, npoly, g, alpha,
                       t, st));
     if (!(flags & MFHE_CTMUL_RESCALE)) return MFHE_OK;
+    return ctmul_rescale(c, d_out0, d_out1, out_poly_stride, npoly, g, t, st);
+}
+
+int ctmul_rescale(mfhe_ctx* c, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride, size_t npoly,
+                  const KsGeom& g, const KsTables& t, hipStream_t st) {
+    const size_t N = c->N;
     // The rescale: mfhe_ntt_moddown(keep = level - 1, drop = limb level - 1) in place on each output, its scratch the
     // key switch's block.  The two outputs are one batch of 2 npoly polynomials when one follows the other at the
     // poly stride (any two single polynomials do); the work per polynomial is the same either way.

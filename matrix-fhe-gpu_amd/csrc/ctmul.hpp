@@ -69,5 +69,10 @@ inline uint64_t* ctmul_d2(const mfhe_ctx* c, size_t npoly, int beta, const KsGeo
 // both outputs by limb level - 1 in place.  ctmul_prepare done by the caller.
 int ctmul_relin_rescale(mfhe_ctx* c, const uint64_t* d_rlk, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride,
                         size_t npoly, const KsGeom& g, int alpha, const KsTables& t, int flags, hipStream_t st);
+// ---- shared with poly.hip ----
+// The rescale half of that tail alone: the ModDown of both outputs ([npoly][level][N] at out_poly_stride) by limb
+// level - 1 in place, scratch the key switch's block (2 npoly level N words), t.rescale built (kKsRescale).
+int ctmul_rescale(mfhe_ctx* c, uint64_t* d_out0, uint64_t* d_out1, size_t out_poly_stride, size_t npoly,
+                  const KsGeom& g, const KsTables& t, hipStream_t st);
 
 }  // namespace mfhe

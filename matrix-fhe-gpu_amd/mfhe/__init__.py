@@ -30,6 +30,8 @@ XCHG_ALLGATHER, XCHG_ALLTOALL = 0, 1
 BCONV_FAST, BCONV_CENTERED = 0, 1
 KS_ADD = 1                      # keyswitch: add the results to what out0 / out1 hold (relinearisation)
 CTMUL_RESCALE = 1               # ctmul: after relinearising, ModDown both outputs by limb level - 1
+POLY_MONOMIAL = 0               # PolyPlan: sum a_i x^i
+POLY_CHEBYSHEV = 1              # PolyPlan: sum a_i T_i(x), slots in [-1, 1]
 SLOT_REAL = 1                   # slot_encode / slot_decode: real slots, N / 2 doubles per polynomial
 SLOT_COEFF = 2                  # slot_encode / slot_decode: residues in the coefficient domain (no NTT)
 RECOMBINE_ROWS_GLOBAL = 1
@@ -168,6 +170,31 @@ _sig("mfhe_ctmat_reserve", [_vp, _int, _int, _sz, _int, _int, _int, _int, _int, 
 _sig("mfhe_ctmat_apply", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _vp, _vp, _sz,
                           _sz, _int, _int, _int, _int, _int, _int, _vp])
 _dbl = ctypes.c_double
+LINCOMB_MAX_TERMS = 64          # ct_lincomb: most terms of one sum (a node of a PolyPlan among them)
+
+
+class PolyInfo(ctypes.Structure):
+    _fields_ = [("basis", _int), ("degree", _int), ("level", _int), ("nnodes", _int), ("nreg", _int),
+                ("nconst", _int), ("nmul", _int), ("depth", _int), ("out_level", _int), ("out_reg", _int),
+                ("in_scale", _dbl), ("out_scale", _dbl)]
+
+
+class PolyNode(ctypes.Structure):
+    _fields_ = [("dst", _int), ("level", _int), ("mul_a", _int), ("mul_b", _int), ("k_mul", _int), ("nterms", _int),
+                ("addend_k", _int), ("term_src", _int * LINCOMB_MAX_TERMS), ("term_k", _int * LINCOMB_MAX_TERMS),
+                ("term_coef", _dbl * LINCOMB_MAX_TERMS), ("addend_coef", _dbl), ("scale_in", _dbl), ("scale_out", _dbl)]
+
+
+_sig("mfhe_ct_lincomb", [_vp, _vp, _vp, _sz, _sz, _int, _vp, _sz, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), _int,
+                         _int, _vp, _vp, _sz, _sz, _int, _vp])
+_sig("mfhe_poly_plan_create", [_vp, ctypes.POINTER(_dbl), _int, _int, _dbl, _int, ctypes.POINTER(_vp)])
+_sig("mfhe_poly_plan_destroy", [_vp])
+_sig("mfhe_poly_plan_info", [_vp, ctypes.POINTER(PolyInfo)])
+_sig("mfhe_poly_plan_node", [_vp, _int, ctypes.POINTER(PolyNode)])
+_sig("mfhe_poly_plan_constant", [_vp, _int, ctypes.POINTER(_int), _u64p, _u64p])
+_sig("mfhe_poly_plan_table", [_vp, ctypes.POINTER(_vp)])
+_sig("mfhe_poly_reserve", [_vp, _vp, _sz, _int, _int, _int, _int])
+_sig("mfhe_poly_apply", [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _int, _int, _int, _int, _vp])
 _sig("mfhe_slot_reserve", [_vp, _sz, _int, _int, _int])
 _sig("mfhe_slot_encode", [_vp, _vp, _sz, _dbl, _vp, _sz, _sz, _int, _int, _int, _int, _vp])
 _sig("mfhe_slot_decode", [_vp, _vp, _sz, _dbl, _vp, _sz, _sz, _int, _int, _vp])
@@ -949,6 +976,68 @@ class Context:
                                    nspecial, flags, _stream_ptr(stream)), "ctmat")
         return out0, out1
 
+    # ---- encrypted polynomial evaluation (include/mfhe.h): scalar sums of ciphertexts and the plans built on them
+    def ct_lincomb(self, x0, x1, k, out0, out1, term_x, term_k, npoly, level, nsrc, nk, addend_k=-1, src_stride=None,
+                   x_poly_stride=None, k_stride=None, out_stride=None, stream=None):
+        """(out0, out1), each [npoly][level][N] = sum_t k[term_k[t]] (x0, x1)[term_x[t]] + (k[addend_k], 0) mod q_r: x0,
+        x1 the components of nsrc ciphertexts, each [nsrc][npoly][>= level rows][N] with a source stride and a poly
+        stride, k [nk][>= level] residues of the constants (or a PolyPlan: its table; nk and k_stride are then the
+        plan's); term_x, term_k Python lists of 1 .. 64 entries.  One launch."""
+        lw = level * self.N
+        pst = lw if x_poly_stride is None else x_poly_stride
+        sst = npoly * pst if src_stride is None else src_stride
+        if isinstance(k, PolyPlan):   # the plan's own table, by its device address
+            kinfo = k.info()
+            kptr, nk, kst = k.table_ptr(), kinfo.nconst, kinfo.level
+        else:
+            kst = level if k_stride is None else k_stride
+            _need(k, (nk - 1) * kst + level if nk > 0 else 0, "ct_lincomb k")
+            kptr = _ptr(k)
+        ost = lw if out_stride is None else out_stride
+        if len(term_x) != len(term_k):
+            raise ValueError("ct_lincomb: term_x and term_k differ in length")
+        for t, what in ((x0, "x0"), (x1, "x1")):
+            self._need_polys(t, npoly, pst, level, self.N, f"ct_lincomb {what} (one source)")
+            _need(t, (nsrc - 1) * sst + (npoly - 1) * pst + lw if npoly and nsrc > 0 else 0, f"ct_lincomb {what}")
+        self._need_polys(out0, npoly, ost, level, self.N, "ct_lincomb out0")
+        self._need_polys(out1, npoly, ost, level, self.N, "ct_lincomb out1")
+        nt = len(term_x)
+        tx, tk = (_int * max(nt, 1))(*term_x), (_int * max(nt, 1))(*term_k)
+        check(lib.mfhe_ct_lincomb(self._h, _ptr(x0), _ptr(x1), sst, pst, nsrc, kptr, kst, nk, tx, tk, nt, addend_k,
+                                  _ptr(out0), _ptr(out1), ost, npoly, level, _stream_ptr(stream)), "ct_lincomb")
+        return out0, out1
+
+    def poly_plan(self, coeffs, basis, in_scale, level) -> "PolyPlan":
+        """The baby-step giant-step plan of sum_i coeffs[i] x^i (POLY_MONOMIAL) or sum_i coeffs[i] T_i(x)
+        (POLY_CHEBYSHEV) for an input at `level` and scale in_scale."""
+        return PolyPlan(self, coeffs, basis, in_scale, level)
+
+    def poly_reserve(self, plan, npoly, key_level, alpha, special_start, nspecial):
+        """Grow the workspace and build every table of every level the plan touches: poly_apply then allocates nothing
+        and copies nothing to the device."""
+        check(lib.mfhe_poly_reserve(self._h, plan.handle, npoly, key_level, alpha, special_start, nspecial),
+              "poly_reserve")
+
+    def poly_apply(self, plan, c0, c1, rlk, out0, out1, npoly, key_level, alpha, special_start, nspecial,
+                   in_stride=None, out_stride=None, stream=None):
+        """(out0, out1), each [npoly][out_level][N] = the plan's polynomial of the ciphertexts (c0, c1), each
+        [npoly][level][N] at the plan's level, with the relinearisation key rlk; the result is at plan.info().out_level
+        and out_scale."""
+        info = plan.info()
+        ist = info.level * self.N if in_stride is None else in_stride
+        ost = info.out_level * self.N if out_stride is None else out_stride
+        self._need_polys(c0, npoly, ist, info.level, self.N, "poly_apply c0")
+        self._need_polys(c1, npoly, ist, info.level, self.N, "poly_apply c1")
+        self._need_polys(out0, npoly, ost, info.out_level, self.N, "poly_apply out0")
+        self._need_polys(out1, npoly, ost, info.out_level, self.N, "poly_apply out1")
+        if rlk is not None:
+            self._need_polys(rlk, -(-key_level // max(alpha, 1)), 2 * (key_level + nspecial) * self.N,
+                             2 * (key_level + nspecial), self.N, "poly_apply rlk")
+        check(lib.mfhe_poly_apply(self._h, plan.handle, _ptr(c0), _ptr(c1), ist, _ptr(rlk), _ptr(out0), _ptr(out1),
+                                  ost, npoly, key_level, alpha, special_start, nspecial, _stream_ptr(stream)),
+              "poly_apply")
+        return out0, out1
+
     # ---- CKKS slots (include/mfhe.h mfhe_slot_*): slot j of a polynomial m is m(zeta^(5^j)), zeta = e^(i pi / N) ----
     def _slot_words(self, t, npoly, stride, flags, what):
         """Checks a slot tensor (float64, interleaved (re, im) unless SLOT_REAL, or complex128) and returns the stride
@@ -1161,6 +1250,68 @@ class Context:
         check(lib.mfhe_decrypt_and_decode_sharded(self._h, ctx_all._h, comm._h, m, _ptr(ct_re), _ptr(ct_im), _ptr(sk),
                                                   _ptr(msg), _stream_ptr(stream)), "decrypt_and_decode_sharded")
         return msg
+
+
+class PolyPlan:
+    """A polynomial evaluation plan (mfhe_poly_plan): the node list of a coefficient vector for one context, input
+    level and input scale, and the device table of its constants' residues."""
+
+    def __init__(self, ctx: "Context", coeffs, basis, in_scale, level):
+        a = [float(v) for v in coeffs]
+        arr = (_dbl * max(len(a), 1))(*a)
+        h = _vp()
+        check(lib.mfhe_poly_plan_create(ctx.handle, arr, len(a) - 1, basis, float(in_scale), level, ctypes.byref(h)),
+              "poly_plan_create")
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> PolyInfo:
+        out = PolyInfo()
+        check(lib.mfhe_poly_plan_info(self._h, ctypes.byref(out)), "poly_plan_info")
+        return out
+
+    def nodes(self) -> list[dict]:
+        """Every node as a dict: dst, level, mul_a, mul_b, k_mul, terms [(src, k, coef)], addend_k, addend_coef, scale_in,
+        scale_out."""
+        out = []
+        for i in range(self.info().nnodes):
+            n = PolyNode()
+            check(lib.mfhe_poly_plan_node(self._h, i, ctypes.byref(n)), "poly_plan_node")
+            out.append(dict(dst=n.dst, level=n.level, mul_a=n.mul_a, mul_b=n.mul_b, k_mul=n.k_mul,
+                            terms=[(n.term_src[j], n.term_k[j], n.term_coef[j]) for j in range(n.nterms)],
+                            addend_k=n.addend_k, addend_coef=n.addend_coef, scale_in=n.scale_in, scale_out=n.scale_out))
+        return out
+
+    def constants(self) -> list[int]:
+        """The constants as Python integers."""
+        out = []
+        for i in range(self.info().nconst):
+            neg, lo, hi = _int(), ctypes.c_uint64(), ctypes.c_uint64()
+            check(lib.mfhe_poly_plan_constant(self._h, i, ctypes.byref(neg), ctypes.byref(lo), ctypes.byref(hi)),
+                  "poly_plan_constant")
+            v = (hi.value << 64) | lo.value
+            out.append(-v if neg.value else v)
+        return out
+
+    def table_ptr(self) -> int:
+        """Device address of the [nconst][level] residue table (row stride `level` words)."""
+        p = _vp()
+        check(lib.mfhe_poly_plan_table(self._h, ctypes.byref(p)), "poly_plan_table")
+        return p.value
+
+    def close(self):
+        if self._h:
+            check(lib.mfhe_poly_plan_destroy(self._h), "poly_plan_destroy")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def fnwt_1d(data, tw, tw_shoup, dmod, dim, coeff_modulus_size, start_modulus_idx=0, batch=1, stream=None):
