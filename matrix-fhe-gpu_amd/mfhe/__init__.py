@@ -34,6 +34,9 @@ POLY_MONOMIAL = 0               # PolyPlan: sum a_i x^i
 POLY_CHEBYSHEV = 1              # PolyPlan: sum a_i T_i(x), slots in [-1, 1]
 SLOT_REAL = 1                   # slot_encode / slot_decode: real slots, N / 2 doubles per polynomial
 SLOT_COEFF = 2                  # slot_encode / slot_decode: residues in the coefficient domain (no NTT)
+RLWE_MASK, RLWE_NOISE, RLWE_SECRET, RLWE_EPHEMERAL, RLWE_NOISE0, RLWE_NOISE1 = 1, 2, 3, 4, 5, 6   # rlwe_*: streams
+RLWE_COEFF = 1                  # rlwe_sample_small / rlwe_lift_small: coefficient domain (no forward NTT)
+RLWE_KEY_SWITCH, RLWE_KEY_RELIN, RLWE_KEY_GALOIS = 0, 1, 2   # rlwe_ksk_gen: where s_from comes from
 RECOMBINE_ROWS_GLOBAL = 1
 RECOMBINE_EXCHANGE_ONLY = 2     # measurement: exchanges only, composes skipped (out untouched)
 RECOMBINE_AFTER_PREV = 4        # the shard was complete when the previous chunked call on the comm was entered
@@ -198,6 +201,16 @@ _sig("mfhe_poly_apply", [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _int,
 _sig("mfhe_slot_reserve", [_vp, _sz, _int, _int, _int])
 _sig("mfhe_slot_encode", [_vp, _vp, _sz, _dbl, _vp, _sz, _sz, _int, _int, _int, _int, _vp])
 _sig("mfhe_slot_decode", [_vp, _vp, _sz, _dbl, _vp, _sz, _sz, _int, _int, _vp])
+_seedp = ctypes.POINTER(ctypes.c_uint32)
+_u64 = ctypes.c_uint64
+_sig("mfhe_rlwe_reserve", [_vp, _sz, _int, _int, _int])
+_sig("mfhe_rlwe_sample_uniform", [_vp, _seedp, _u64, _vp, _sz, _sz, _int, _int, _int, _vp])
+_sig("mfhe_rlwe_sample_small", [_vp, _seedp, _int, _u64, _vp, _sz, _sz, _int, _int, _int, _int, _vp])
+_sig("mfhe_rlwe_lift_small", [_vp, _vp, _sz, _vp, _sz, _sz, _int, _int, _int, _int, _vp])
+_sig("mfhe_rlwe_encrypt_sk", [_vp, _seedp, _u64, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _int, _int, _int, _vp])
+_sig("mfhe_rlwe_ksk_gen", [_vp, _seedp, _u64, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp])
+_sig("mfhe_rlwe_encrypt_pk", [_vp, _seedp, _u64, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _int, _vp])
+_sig("mfhe_rlwe_decrypt", [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _int, _vp])
 for _n in ("mfhe_wcrt_fwd", "mfhe_wcrt_inv", "mfhe_wcrt_fwd_vector", "mfhe_wcrt_fwd_centered",
            "mfhe_wcrt_inv_centered", "mfhe_wdft_fwd", "mfhe_wdft_inv", "mfhe_matrix_to_poly", "mfhe_poly_to_matrix",
            "mfhe_keygen"):
@@ -352,6 +365,33 @@ def _ptr(t) -> int:
     if not t.is_contiguous():
         raise ValueError("mfhe needs contiguous tensors")
     return t.data_ptr()
+
+
+class Seed:
+    """The 256-bit seed of the rlwe_* draws (32 bytes, from os.urandom by default) with a counter of polynomial ids:
+    take(n) returns the first of n ids never handed out before, so calls that share a Seed never reuse a
+    (seed, stream, id).  The library itself obtains no entropy and keeps no state."""
+
+    def __init__(self, key: bytes = None, next_id: int = 0):
+        key = os.urandom(32) if key is None else bytes(key)
+        if len(key) != 32:
+            raise ValueError("a Seed is 32 bytes")
+        self.key, self.next_id = key, int(next_id)
+        self.words = (ctypes.c_uint32 * 8)(*[int.from_bytes(key[4 * i:4 * i + 4], "little") for i in range(8)])
+
+    def take(self, n: int = 1) -> int:
+        if n < 0 or self.next_id + n > 1 << 64:
+            raise ValueError("Seed: the 64-bit id space is exhausted")
+        first, self.next_id = self.next_id, self.next_id + n
+        return first
+
+
+def _seed_words(seed):
+    if isinstance(seed, Seed):
+        return seed.words
+    if seed is None:
+        return None
+    return Seed(seed).words
 
 
 class Context:
@@ -1081,6 +1121,112 @@ class Context:
         check(lib.mfhe_slot_decode(self._h, _ptr(src), ist, float(scale), _ptr(slots), sst, npoly, level, flags,
                                    _stream_ptr(stream)), "slot_decode")
         return slots
+
+    # ---- RLWE keys, encryption, decryption (include/mfhe.h mfhe_rlwe_*): seeded ChaCha20 draws on the key switch's
+    # layout; `seed` is a Seed (or 32 bytes), `first_id` the first polynomial id of the call (Seed.take hands out ranges)
+    def rlwe_reserve(self, npoly, level, special_start=0, nspecial=0):
+        """Grow the workspace for every rlwe_* call at this geometry: they then allocate nothing and copy nothing to
+        the device (rlwe_ksk_gen at key_level = level: npoly >= beta)."""
+        check(lib.mfhe_rlwe_reserve(self._h, npoly, level, special_start, nspecial), "rlwe_reserve")
+
+    def rlwe_sample_uniform(self, seed, first_id, out, npoly, level, special_start=0, nspecial=0, out_stride=None,
+                            stream=None):
+        """out [npoly][level + nspecial][N] = the mask residues of ids first_id .. first_id + npoly - 1."""
+        rows = level + nspecial
+        ost = rows * self.N if out_stride is None else out_stride
+        self._need_polys(out, npoly, ost, rows, self.N, "rlwe_sample_uniform out")
+        check(lib.mfhe_rlwe_sample_uniform(self._h, _seed_words(seed), first_id, _ptr(out), ost, npoly, level,
+                                           special_start, nspecial, _stream_ptr(stream)), "rlwe_sample_uniform")
+        return out
+
+    def rlwe_sample_small(self, seed, stream_id, first_id, out, npoly, level, special_start=0, nspecial=0, flags=0,
+                          out_stride=None, stream=None):
+        """out [npoly][level + nspecial][N] = the residues of the small integers of stream `stream_id` (RLWE_NOISE ..
+        RLWE_NOISE1), in the evaluation domain unless RLWE_COEFF.  A secret key: RLWE_SECRET at key_level + K rows."""
+        rows = level + nspecial
+        ost = rows * self.N if out_stride is None else out_stride
+        self._need_polys(out, npoly, ost, rows, self.N, "rlwe_sample_small out")
+        check(lib.mfhe_rlwe_sample_small(self._h, _seed_words(seed), stream_id, first_id, _ptr(out), ost, npoly, level,
+                                         special_start, nspecial, flags, _stream_ptr(stream)), "rlwe_sample_small")
+        return out
+
+    def rlwe_lift_small(self, coeffs, out, npoly, level, special_start=0, nspecial=0, flags=0, coeff_stride=None,
+                        out_stride=None, stream=None):
+        """out [npoly][level + nspecial][N] = the residues of the int32 coefficients [npoly][N] (coeff_stride in
+        int32), in the evaluation domain unless RLWE_COEFF: the caller's own small polynomials."""
+        import torch
+        if coeffs.dtype != torch.int32:
+            raise ValueError(f"rlwe_lift_small: coefficients are int32, not {coeffs.dtype}")
+        rows = level + nspecial
+        cst = self.N if coeff_stride is None else coeff_stride
+        ost = rows * self.N if out_stride is None else out_stride
+        if cst < self.N:
+            raise ValueError("rlwe_lift_small: coefficient stride smaller than N")
+        if npoly and coeffs.numel() < (npoly - 1) * cst + self.N:
+            raise ValueError("rlwe_lift_small coeffs: tensor smaller than the polynomials it holds")
+        self._need_polys(out, npoly, ost, rows, self.N, "rlwe_lift_small out")
+        check(lib.mfhe_rlwe_lift_small(self._h, _ptr(coeffs), cst, _ptr(out), ost, npoly, level, special_start,
+                                       nspecial, flags, _stream_ptr(stream)), "rlwe_lift_small")
+        return out
+
+    def rlwe_encrypt_sk(self, seed, first_id, s, m, c0, c1, npoly, level, special_start=0, nspecial=0, m_stride=None,
+                        out_stride=None, stream=None):
+        """(c0, c1) [npoly][level + nspecial][N] with c1 = a, c0 = m + e - a s under the secret s [level + nspecial][N];
+        m None encrypts zero (a public key is that call with npoly = 1)."""
+        rows = level + nspecial
+        mst = rows * self.N if m_stride is None else m_stride
+        ost = rows * self.N if out_stride is None else out_stride
+        self._need_polys(s, 1, rows * self.N, rows, self.N, "rlwe_encrypt_sk s")
+        if m is not None:
+            self._need_polys(m, npoly, mst, rows, self.N, "rlwe_encrypt_sk m")
+        self._need_polys(c0, npoly, ost, rows, self.N, "rlwe_encrypt_sk c0")
+        self._need_polys(c1, npoly, ost, rows, self.N, "rlwe_encrypt_sk c1")
+        check(lib.mfhe_rlwe_encrypt_sk(self._h, _seed_words(seed), first_id, _ptr(s), _ptr(m), mst, _ptr(c0), _ptr(c1),
+                                       ost, npoly, level, special_start, nspecial, _stream_ptr(stream)),
+              "rlwe_encrypt_sk")
+        return c0, c1
+
+    def rlwe_ksk_gen(self, seed, first_id, kind, s_to, ksk, key_level, alpha, special_start, nspecial, s_from=None,
+                     galois_elt=1, stream=None):
+        """ksk [beta][2][key_level + K][N]: a switching key to s_to from s_from (RLWE_KEY_SWITCH), from s_to^2
+        (RLWE_KEY_RELIN) or from sigma_g(s_to) (RLWE_KEY_GALOIS); digit j draws at id first_id + j."""
+        rows, beta = key_level + nspecial, -(-key_level // max(alpha, 1))
+        self._need_polys(s_to, 1, rows * self.N, rows, self.N, "rlwe_ksk_gen s_to")
+        if s_from is not None:
+            self._need_polys(s_from, 1, rows * self.N, rows, self.N, "rlwe_ksk_gen s_from")
+        self._need_polys(ksk, beta, 2 * rows * self.N, 2 * rows, self.N, "rlwe_ksk_gen ksk")
+        check(lib.mfhe_rlwe_ksk_gen(self._h, _seed_words(seed), first_id, kind, galois_elt, _ptr(s_from), _ptr(s_to),
+                                    _ptr(ksk), key_level, alpha, special_start, nspecial, _stream_ptr(stream)),
+              "rlwe_ksk_gen")
+        return ksk
+
+    def rlwe_encrypt_pk(self, seed, first_id, pk0, pk1, m, c0, c1, npoly, level, m_stride=None, out_stride=None,
+                        stream=None):
+        """(c0, c1) [npoly][level][N] = (pk0 u + e0 + m, pk1 u + e1) on rows [0, level) of the public key; m None
+        encrypts zero."""
+        mst = level * self.N if m_stride is None else m_stride
+        ost = level * self.N if out_stride is None else out_stride
+        self._need_polys(pk0, 1, level * self.N, level, self.N, "rlwe_encrypt_pk pk0")
+        self._need_polys(pk1, 1, level * self.N, level, self.N, "rlwe_encrypt_pk pk1")
+        if m is not None:
+            self._need_polys(m, npoly, mst, level, self.N, "rlwe_encrypt_pk m")
+        self._need_polys(c0, npoly, ost, level, self.N, "rlwe_encrypt_pk c0")
+        self._need_polys(c1, npoly, ost, level, self.N, "rlwe_encrypt_pk c1")
+        check(lib.mfhe_rlwe_encrypt_pk(self._h, _seed_words(seed), first_id, _ptr(pk0), _ptr(pk1), _ptr(m), mst,
+                                       _ptr(c0), _ptr(c1), ost, npoly, level, _stream_ptr(stream)), "rlwe_encrypt_pk")
+        return c0, c1
+
+    def rlwe_decrypt(self, c0, c1, s, out, npoly, rows, in_stride=None, out_stride=None, stream=None):
+        """out [npoly][rows][N] = c0 + c1 s on rows [0, rows); rows = min(level, 2) is all slot_decode reads."""
+        ist = rows * self.N if in_stride is None else in_stride
+        ost = rows * self.N if out_stride is None else out_stride
+        self._need_polys(c0, npoly, ist, rows, self.N, "rlwe_decrypt c0")
+        self._need_polys(c1, npoly, ist, rows, self.N, "rlwe_decrypt c1")
+        self._need_polys(s, 1, rows * self.N, rows, self.N, "rlwe_decrypt s")
+        self._need_polys(out, npoly, ost, rows, self.N, "rlwe_decrypt out")
+        check(lib.mfhe_rlwe_decrypt(self._h, _ptr(c0), _ptr(c1), ist, _ptr(s), _ptr(out), ost, npoly, rows,
+                                    _stream_ptr(stream)), "rlwe_decrypt")
+        return out
 
     def crt_recombine_sharded(self, comm: "Comm", mode, shard, npoly, ncoeff, out, out_stride=1, stream=None):
         """RCCL exchange of this rank's [npoly][L/G][ncoeff] residue shard + compose of its polynomial slice
