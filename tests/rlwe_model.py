@@ -30,10 +30,13 @@ def _quarter(x, a, b, c, d):
 
 
 def chacha20_blocks(key_words, counters, nonce_words):
-    """out [len(counters)][16] uint32: the ChaCha20 block of every 32-bit counter under one key and nonce."""
+    """out [len(counters)][16] uint32: the ChaCha20 block of every 32-bit counter under one key and nonce.  A nonce word
+    may also be an array with one entry per counter: every lane then has its own nonce (small_values_ids and
+    mask_residues_ids below draw all their (id, counter) pairs in one call this way)."""
     counters = np.asarray(counters, dtype=np.uint64)
     assert (counters < (1 << 32)).all()
     n = len(counters)
+    assert all(np.ndim(v) == 0 or np.shape(v) == (n,) for v in nonce_words)
     const = [np.full(n, v, dtype=np.uint32) for v in SIGMA + tuple(key_words)]
     init = const + [counters.astype(np.uint32)] + [np.full(n, v, dtype=np.uint32) for v in nonce_words]
     x = [v.copy() for v in init]
@@ -84,6 +87,44 @@ def small_values(key_words, stream, pid, n):
     assert stream in SMALL_STREAMS
     w = small_words(key_words, stream, pid, n)
     return ternary(w) if stream in TERNARY_STREAMS else noise(w)
+
+
+def _id_lanes(first_word, ids, nblocks):
+    """(counters, nonce words) of nblocks blocks of every id, id-major: one lane per (id, counter) pair."""
+    ids = [int(i) for i in ids]
+    assert all(0 <= i < 1 << 64 for i in ids)
+    lo = np.repeat(np.array([i & 0xFFFFFFFF for i in ids], dtype=np.uint32), nblocks)
+    hi = np.repeat(np.array([i >> 32 for i in ids], dtype=np.uint32), nblocks)
+    return np.tile(np.arange(nblocks, dtype=np.uint64), len(ids)), [first_word, lo, hi]
+
+
+def small_values_ids(key_words, stream, ids, n):
+    """[len(ids)][n] int64: small_values of every id, from one ChaCha call over all (id, counter) pairs and the two
+    maps restated on uint64 arrays (tests/test_rlwe_cpu.py compares it with the per-id function)."""
+    assert stream in SMALL_STREAMS
+    nb = (n + 7) // 8
+    counters, nw = _id_lanes(nonce(stream, 0, 0)[0], ids, nb)
+    out = chacha20_blocks(key_words, counters, nw).astype(np.uint64).reshape(len(ids), nb * 8, 2)
+    lo, hi = out[:, :n, 0], out[:, :n, 1]
+    if stream in TERNARY_STREAMS:
+        # floor(3 w / 2^64) with w = 2^32 hi + lo: 3 hi + floor(3 lo / 2^32) is below 2^34
+        three = np.uint64(3)
+        return (((three * hi + ((three * lo) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64) - 1)
+    w = lo | (hi << np.uint64(32))
+    one = np.uint64(1)
+    v = np.zeros(w.shape, dtype=np.int64)
+    for k in range(NOISE_BITS):
+        v += ((w >> np.uint64(k)) & one).astype(np.int64) - ((w >> np.uint64(NOISE_BITS + k)) & one).astype(np.int64)
+    return v
+
+
+def mask_residues_ids(key_words, limb, ids, n, q):
+    """[len(ids)][n] uint64: mask_residues of every id, from one ChaCha call over all (id, counter) pairs."""
+    nb = (n + 3) // 4
+    counters, nw = _id_lanes(nonce(MASK, limb, 0)[0], ids, nb)
+    w = chacha20_blocks(key_words, counters, nw).astype(object).reshape(len(ids), nb * 4, 4)[:, :n]
+    v = w[:, :, 0] | (w[:, :, 1] << 32) | (w[:, :, 2] << 64) | (w[:, :, 3] << 96)
+    return (v % int(q)).astype(np.uint64)
 
 
 def row_limbs(level, special_start, nspecial):

@@ -209,12 +209,48 @@ def test_tensor_folds_work_items_over_grid_z(mfhe):
 # ---------------------------------------------------------------------------------------------------------------
 # 4. the driver against m n calls of ctmul
 # ---------------------------------------------------------------------------------------------------------------
+def _check_against_separate_products(mfhe, ctx, mod, rng, rlk, m, n, k, npoly, level, key_level, alpha, sp, nsp, opad):
+    """ctmat on fresh random operands against m n calls of ctmul, one per entry, with the same flags (with
+    CTMUL_RESCALE rows [0, level - 1) are compared); the outputs lie opad words apart and their pads stay canaries.
+    (tests/test_client_shapes_gpu.py runs it where the NTT plan changes.)"""
+    import torch
+    N = ctx.N
+    lw = level * N
+    a0, a1 = (_random_rows(rng, (m, k, npoly), mod[:level], N) for _ in range(2))
+    b0, b1 = (_random_rows(rng, (k, n, npoly), mod[:level], N) for _ in range(2))
+    A0, A1 = (_Matrix(mfhe, m, k, npoly, level, N, 2, 4, 2, 0, x) for x in (a0, a1))
+    B0, B1 = (_Matrix(mfhe, k, n, npoly, level, N, 0, 6, 0, 0, x) for x in (b0, b1))
+    for flags in (0, mfhe.CTMUL_RESCALE):
+        keep = level - 1 if flags else level
+        msg = f"alpha {alpha} K {nsp} level {level} flags {flags}"
+        o0, o1 = (_polys(mfhe, m * n * npoly, level, N, opad) for _ in range(2))
+        ctx.ctmat(A0.t, A1.t, B0.t, B1.t, rlk, o0.t, o1.t, m, n, k, npoly, level, key_level, alpha, sp, nsp,
+                  flags, a_strides=A0.strides, b_strides=B0.strides, out_stride=o0.stride)
+        torch.cuda.synchronize()
+        got = [o.blocks((m, n, npoly, level, N)) for o in (o0, o1)]
+        for o in (o0, o1):
+            o.check_pads()
+        for i in range(m):
+            for j in range(n):
+                e0, e1 = (torch.zeros(npoly * lw, dtype=torch.int64, device="cuda") for _ in range(2))
+                ctx.ctmul(A0.t[i * A0.rs:], A1.t[i * A1.rs:], B0.t[j * B0.cs:], B1.t[j * B1.cs:], rlk, e0, e1,
+                          npoly, level, key_level, alpha, sp, nsp, k, flags, a_term_stride=A0.cs,
+                          a_poly_stride=A0.pst, b_term_stride=B0.rs, b_poly_stride=B0.pst)
+                torch.cuda.synchronize()
+                for c, e in enumerate((e0, e1)):
+                    np.testing.assert_array_equal(
+                        got[c][i, j][:, :keep], mfhe.to_host_u64(e).reshape(npoly, level, N)[:, :keep],
+                        err_msg=f"out{c}[{i}][{j}] " + msg)
+    for blk in (A0, A1, B0, B1):
+        np.testing.assert_array_equal(blk.get(), blk.src)
+        blk.check_pads()
+
+
 @CLASSES
 @LOGNS
 def test_ctmat_equals_the_separate_products(mfhe, log_n, bits):
     """ctmat of a 2 x 3 product of 3 terms and 2 polynomials = six calls of ctmul, one per entry, on the same operands
     with the same flags (with CTMUL_RESCALE rows [0, level - 1) are compared); the pads of the outputs stay canaries."""
-    import torch
     ctx, mod, N = _ctx(log_n, bits), _moduli(log_n, bits), 1 << log_n
     rng = np.random.default_rng(70 + log_n)
     m, n, k, npoly = 2, 3, 3, 2
@@ -222,35 +258,8 @@ def test_ctmat_equals_the_separate_products(mfhe, log_n, bits):
         kmod = [mod[l] for l in _row_limbs(key_level, sp, nsp)]
         rlk = mfhe.to_device_u64(_random_rows(rng, (-(-key_level // alpha), 2), kmod, N).ravel())
         for level in levels:
-            lw = level * N
-            a0, a1 = (_random_rows(rng, (m, k, npoly), mod[:level], N) for _ in range(2))
-            b0, b1 = (_random_rows(rng, (k, n, npoly), mod[:level], N) for _ in range(2))
-            A0, A1 = (_Matrix(mfhe, m, k, npoly, level, N, 2, 4, 2, 0, x) for x in (a0, a1))
-            B0, B1 = (_Matrix(mfhe, k, n, npoly, level, N, 0, 6, 0, 0, x) for x in (b0, b1))
-            for flags in (0, mfhe.CTMUL_RESCALE):
-                keep = level - 1 if flags else level
-                msg = f"alpha {alpha} K {nsp} level {level} flags {flags}"
-                o0, o1 = (_polys(mfhe, m * n * npoly, level, N, 2 if log_n == 10 else 3) for _ in range(2))
-                ctx.ctmat(A0.t, A1.t, B0.t, B1.t, rlk, o0.t, o1.t, m, n, k, npoly, level, key_level, alpha, sp, nsp,
-                          flags, a_strides=A0.strides, b_strides=B0.strides, out_stride=o0.stride)
-                torch.cuda.synchronize()
-                got = [o.blocks((m, n, npoly, level, N)) for o in (o0, o1)]
-                for o in (o0, o1):
-                    o.check_pads()
-                for i in range(m):
-                    for j in range(n):
-                        e0, e1 = (torch.zeros(npoly * lw, dtype=torch.int64, device="cuda") for _ in range(2))
-                        ctx.ctmul(A0.t[i * A0.rs:], A1.t[i * A1.rs:], B0.t[j * B0.cs:], B1.t[j * B1.cs:], rlk, e0, e1,
-                                  npoly, level, key_level, alpha, sp, nsp, k, flags, a_term_stride=A0.cs,
-                                  a_poly_stride=A0.pst, b_term_stride=B0.rs, b_poly_stride=B0.pst)
-                        torch.cuda.synchronize()
-                        for c, e in enumerate((e0, e1)):
-                            np.testing.assert_array_equal(
-                                got[c][i, j][:, :keep], mfhe.to_host_u64(e).reshape(npoly, level, N)[:, :keep],
-                                err_msg=f"out{c}[{i}][{j}] " + msg)
-            for blk in (A0, A1, B0, B1):
-                np.testing.assert_array_equal(blk.get(), blk.src)
-                blk.check_pads()
+            _check_against_separate_products(mfhe, ctx, mod, rng, rlk, m, n, k, npoly, level, key_level, alpha, sp, nsp,
+                                              2 if log_n == 10 else 3)
 
 
 # ---------------------------------------------------------------------------------------------------------------

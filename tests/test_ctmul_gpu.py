@@ -151,13 +151,61 @@ def test_tensor_folds_polynomials_over_grid_z(mfhe):
 # ---------------------------------------------------------------------------------------------------------------
 # 4. the driver against the composition of the public calls
 # ---------------------------------------------------------------------------------------------------------------
+def _check_against_the_composition(mfhe, ctx, mod, rng, rlk, npoly, T, level, key_level, alpha, sp, k):
+    """ctmul on fresh random operands of T terms against ctmul_tensor, keyswitch(KS_ADD) of d2 and, with CTMUL_RESCALE,
+    ntt_moddown by limb level - 1 in place on each output: general and square, 1 and 3 terms, both flags, the outputs
+    as two padded allocations and as the halves of one; the operands are untouched.  (tests/test_client_shapes_gpu.py
+    runs it where the NTT plan changes.)"""
+    import torch
+    n = ctx.N
+    lw = level * n
+    a0, a1, b0, b1 = (_random_rows(rng, (T, npoly), mod[:level], n) for _ in range(4))
+    A0, A1 = (_operand(mfhe, x, npoly, 2, 4, 0) for x in (a0, a1))
+    B0, B1 = (_operand(mfhe, x, npoly, 0, 6, 0) for x in (b0, b1))
+    for square in (False, True):
+        tb0, tb1 = (None, None) if square else (B0.t, B1.t)
+        strides = dict(a_term_stride=A0.tst, a_poly_stride=A0.pst, b_term_stride=B0.tst, b_poly_stride=B0.pst)
+        for nt in (1, 3):
+            d0, d1, d2 = (torch.zeros(npoly * lw, dtype=torch.int64, device="cuda") for _ in range(3))
+            ctx.ctmul_tensor(A0.t, A1.t, tb0, tb1, d0, d1, d2, npoly, level, nt, **strides)
+            ctx.keyswitch(d2, rlk, d0, d1, npoly, level, key_level, alpha, sp, k, mfhe.KS_ADD)
+            torch.cuda.synchronize()
+            want = {0: [mfhe.to_host_u64(d).reshape(npoly, level, n).copy() for d in (d0, d1)]}
+            for d in (d0, d1):
+                ctx.ntt_moddown(d, d, npoly, level - 1, level - 1, 1, in_stride=lw, out_stride=lw)
+            torch.cuda.synchronize()
+            want[mfhe.CTMUL_RESCALE] = [mfhe.to_host_u64(d).reshape(npoly, level, n)[:, :level - 1].copy()
+                                        for d in (d0, d1)]
+            for flags in (0, mfhe.CTMUL_RESCALE):
+                keep = level - 1 if flags else level
+                msg = f"alpha {alpha} K {k} level {level} nterms {nt} square {square} flags {flags}"
+                o0, o1 = _polys(mfhe, npoly, level, n, 3), _polys(mfhe, npoly, level, n, 3)
+                ctx.ctmul(A0.t, A1.t, tb0, tb1, rlk, o0.t, o1.t, npoly, level, key_level, alpha, sp, k, nt,
+                          flags, out_stride=o0.stride, **strides)
+                both = torch.full((2 * npoly * lw + 2,), CANARY - (1 << 64), dtype=torch.int64, device="cuda")
+                ctx.ctmul(A0.t, A1.t, tb0, tb1, rlk, both[:npoly * lw], both[npoly * lw:], npoly, level,
+                          key_level, alpha, sp, k, nt, flags, **strides)
+                torch.cuda.synchronize()
+                hb = mfhe.to_host_u64(both)
+                assert (hb[-2:] == np.uint64(CANARY)).all(), msg
+                for c, o in enumerate((o0, o1)):
+                    np.testing.assert_array_equal(o.blocks((npoly, level, n))[:, :keep], want[flags][c],
+                                                  err_msg=f"out{c} (two allocations) " + msg)
+                    o.check_pads()
+                    np.testing.assert_array_equal(
+                        hb[c * npoly * lw:(c + 1) * npoly * lw].reshape(npoly, level, n)[:, :keep],
+                        want[flags][c], err_msg=f"out{c} (one allocation) " + msg)
+    for blk in (A0, A1, B0, B1):
+        np.testing.assert_array_equal(blk.blocks(blk.src.shape), blk.src)
+        blk.check_pads()
+
+
 @CLASSES
 @LOGNS
 def test_ctmul_equals_the_composition(mfhe, log_n, bits):
     """ctmul = ctmul_tensor, keyswitch(KS_ADD) of d2 and, with CTMUL_RESCALE, ntt_moddown by limb level - 1 in place on
     each output (rows [0, level - 1) compared).  The outputs are once two padded allocations (the rescale runs per
     output) and once the halves of one dense allocation (it runs as one batch)."""
-    import torch
     ctx, mod, n = _ctx(log_n, bits), _moduli(log_n, bits), 1 << log_n
     rng = np.random.default_rng(50 + log_n)
     npoly, T = 2, 3
@@ -165,46 +213,7 @@ def test_ctmul_equals_the_composition(mfhe, log_n, bits):
         kmod = [mod[l] for l in _row_limbs(key_level, sp, k)]
         rlk = mfhe.to_device_u64(_random_rows(rng, (-(-key_level // alpha), 2), kmod, n).ravel())
         for level in levels:
-            lw = level * n
-            a0, a1, b0, b1 = (_random_rows(rng, (T, npoly), mod[:level], n) for _ in range(4))
-            A0, A1 = (_operand(mfhe, x, npoly, 2, 4, 0) for x in (a0, a1))
-            B0, B1 = (_operand(mfhe, x, npoly, 0, 6, 0) for x in (b0, b1))
-            for square in (False, True):
-                tb0, tb1 = (None, None) if square else (B0.t, B1.t)
-                strides = dict(a_term_stride=A0.tst, a_poly_stride=A0.pst, b_term_stride=B0.tst, b_poly_stride=B0.pst)
-                for nt in (1, 3):
-                    d0, d1, d2 = (torch.zeros(npoly * lw, dtype=torch.int64, device="cuda") for _ in range(3))
-                    ctx.ctmul_tensor(A0.t, A1.t, tb0, tb1, d0, d1, d2, npoly, level, nt, **strides)
-                    ctx.keyswitch(d2, rlk, d0, d1, npoly, level, key_level, alpha, sp, k, mfhe.KS_ADD)
-                    torch.cuda.synchronize()
-                    want = {0: [mfhe.to_host_u64(d).reshape(npoly, level, n).copy() for d in (d0, d1)]}
-                    for d in (d0, d1):
-                        ctx.ntt_moddown(d, d, npoly, level - 1, level - 1, 1, in_stride=lw, out_stride=lw)
-                    torch.cuda.synchronize()
-                    want[mfhe.CTMUL_RESCALE] = [mfhe.to_host_u64(d).reshape(npoly, level, n)[:, :level - 1].copy()
-                                                for d in (d0, d1)]
-                    for flags in (0, mfhe.CTMUL_RESCALE):
-                        keep = level - 1 if flags else level
-                        msg = f"alpha {alpha} K {k} level {level} nterms {nt} square {square} flags {flags}"
-                        o0, o1 = _polys(mfhe, npoly, level, n, 3), _polys(mfhe, npoly, level, n, 3)
-                        ctx.ctmul(A0.t, A1.t, tb0, tb1, rlk, o0.t, o1.t, npoly, level, key_level, alpha, sp, k, nt,
-                                  flags, out_stride=o0.stride, **strides)
-                        both = torch.full((2 * npoly * lw + 2,), CANARY - (1 << 64), dtype=torch.int64, device="cuda")
-                        ctx.ctmul(A0.t, A1.t, tb0, tb1, rlk, both[:npoly * lw], both[npoly * lw:], npoly, level,
-                                  key_level, alpha, sp, k, nt, flags, **strides)
-                        torch.cuda.synchronize()
-                        hb = mfhe.to_host_u64(both)
-                        assert (hb[-2:] == np.uint64(CANARY)).all(), msg
-                        for c, o in enumerate((o0, o1)):
-                            np.testing.assert_array_equal(o.blocks((npoly, level, n))[:, :keep], want[flags][c],
-                                                          err_msg=f"out{c} (two allocations) " + msg)
-                            o.check_pads()
-                            np.testing.assert_array_equal(
-                                hb[c * npoly * lw:(c + 1) * npoly * lw].reshape(npoly, level, n)[:, :keep],
-                                want[flags][c], err_msg=f"out{c} (one allocation) " + msg)
-            for blk in (A0, A1, B0, B1):
-                np.testing.assert_array_equal(blk.blocks(blk.src.shape), blk.src)
-                blk.check_pads()
+            _check_against_the_composition(mfhe, ctx, mod, rng, rlk, npoly, T, level, key_level, alpha, sp, k)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -182,6 +182,29 @@ def test_mask_residues_are_canonical_and_spread():
     assert abs(top - len(a) / 2) <= 5 * math.sqrt(len(a) / 4)
 
 
+def test_the_batched_draws_equal_the_per_id_functions():
+    """small_values_ids and mask_residues_ids (one ChaCha call with a nonce per lane) against small_values and
+    mask_residues id by id, on ids on both sides of the id's word boundary and at the end of its range, at a length
+    that is no whole number of blocks and at one of several blocks; and a one-id call of the lane form of
+    chacha20_blocks against the scalar form."""
+    ids = [0, 1, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, (1 << 63) + 5, (1 << 64) - 1]
+    nw = rm.nonce(rm.MASK, 3, ids[2])
+    lanes = [nw[0], np.full(4, nw[1], dtype=np.uint32), np.full(4, nw[2], dtype=np.uint32)]
+    np.testing.assert_array_equal(rm.chacha20_blocks(KW, np.arange(4), lanes), rm.chacha20_blocks(KW, np.arange(4), nw))
+    for n in (13, 64):
+        for stream in rm.SMALL_STREAMS:
+            got = rm.small_values_ids(KW, stream, ids, n)
+            assert got.shape == (len(ids), n) and got.dtype == np.int64
+            for row, pid in zip(got, ids):
+                np.testing.assert_array_equal(row, rm.small_values(KW, stream, pid, n), err_msg=f"{stream} {pid}")
+        for limb, q in ((0, (1 << 61) - 1), (13, 65537), (255, (1 << 45) - 229)):
+            got = rm.mask_residues_ids(KW, limb, ids, n, q)
+            assert got.shape == (len(ids), n) and got.dtype == np.uint64
+            for row, pid in zip(got, ids):
+                np.testing.assert_array_equal(row, rm.mask_residues(KW, limb, pid, n, q), err_msg=f"{limb} {pid}")
+    assert len({tuple(r) for r in rm.small_values_ids(KW, rm.NOISE, ids, 64).tolist()}) == len(ids)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 4. the C ABI
 # ---------------------------------------------------------------------------------------------------------------

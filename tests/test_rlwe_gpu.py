@@ -2,7 +2,9 @@
 tests/rlwe_model.py, every fused call against its definition through the public calls and Python integers, the noise
 of a public-key encryption and of a generated switching key under their bounds, graph capture after the reserve call,
 argument errors, and one computation end to end -- keys, encode, encrypt, polynomial, decrypt, decode -- with no host
-arithmetic between the encoder and the decoder."""
+arithmetic between the encoder and the decoder.  Everything here runs at N <= 2^10 on at most 3 polynomials;
+tests/test_client_shapes_gpu.py reaches the launch shapes beyond that: more than one workgroup per row, more than one
+run of polynomials, the small kernel's fold over grid y and z, and N = 2^14 and 2^16 where the NTT plan changes."""
 import ctypes
 import functools
 
@@ -84,11 +86,11 @@ def _dev(mfhe, a):
     return mfhe.to_device_u64(np.ascontiguousarray(a).ravel())
 
 
-def _secret(mfhe, ctx, pid, level, k, n):
+def _secret(mfhe, ctx, pid, level, k, n, sp=SP):
     """(device tensor, host rows) of the ternary secret of id `pid` at level + k rows, evaluation domain."""
     import torch
     t = torch.zeros((level + k) * n, dtype=torch.int64, device="cuda")
-    ctx.rlwe_sample_small(KEY, mfhe.RLWE_SECRET, pid, t, 1, level, SP, k)
+    ctx.rlwe_sample_small(KEY, mfhe.RLWE_SECRET, pid, t, 1, level, sp, k)
     torch.cuda.synchronize()
     return t, mfhe.to_host_u64(t).reshape(level + k, n).copy()
 
