@@ -426,9 +426,10 @@ static int decode_impl(mfhe_ctx* c, const uint64_t* ev_re, const uint64_t* ev_im
     RC(need_wcrt(c));
     if (!ev_re || !ev_im || !msg) return set_error(MFHE_EINVAL, "mfhe_decode: null pointer");
     RC(ensure_xy(c));
-    Bump b0{(char*)c->ws};
+    Bump b0{nullptr};
     if (!pb) {
-        RC(ensure_ws(c));
+        RC(ensure_ws(c));   // may allocate or move the workspace: take its address only afterwards
+        b0.p = (char*)c->ws;
         pb = &b0;
     }
     const Geo2 g = geo(c);

@@ -293,6 +293,16 @@ def test_encrypt_decrypt_vs_oracle_c4_moduli(mfhe, orc):
     ctx.close()
 
 
+def test_encrypt_decrypt_vs_oracle_n32(mfhe, orc):
+    """The same bit-exact check at n = 32 (ring_row.hpp ring_mul_row<5> and the n = 32 encrypt / decrypt row kernels
+    of he.hip run nowhere else), on two limbs so the oracle's __int128 W-CRT stays within seconds."""
+    n = 32
+    ctx = mfhe.Context(RNS[:2], 5, CONV)
+    h = orc.HE(n, RNS[:2], 2.0 ** 35)
+    _encrypt_decrypt_vs_oracle(mfhe, orc, n, ctx, h, RNS[:2])
+    ctx.close()
+
+
 def _encrypt_decrypt_vs_oracle(mfhe, orc, n, ctx, h, moduli):
     import torch
     Lq = len(moduli)
@@ -350,7 +360,7 @@ def _encrypt_decrypt_vs_oracle(mfhe, orc, n, ctx, h, moduli):
     np.testing.assert_array_equal(mfhe.to_host_u64(ev), h.decrypt_to_eval(gre, sk_ref))
 
 
-@pytest.mark.parametrize("n,L", [(8, 11), (16, 3), (64, 11), (64, 1), (8, 16), (64, 16)])
+@pytest.mark.parametrize("n,L", [(8, 11), (16, 3), (64, 11), (64, 1), (8, 16), (64, 16), (32, 11)])
 def test_encrypt_noise_small_operand_gemm_matches_factored(mfhe, n, L):
     """MFHE_OPT_ENC_E_SMALL (r06): the encrypt's Gaussian noise enters its W-CRT forward as the dense product with its
     one signed digit (|e| <= 27 from the Box-Muller bound) and is never written as residues.  1 (default): wcrt_mfma.hpp
@@ -397,7 +407,7 @@ def test_encrypt_noise_small_operand_gemm_matches_factored(mfhe, n, L):
     ctx.close()
 
 
-@pytest.mark.parametrize("n,L", [(4, 2), (8, 11), (16, 3), (64, 11)])
+@pytest.mark.parametrize("n,L", [(4, 2), (8, 11), (16, 3), (64, 11), (32, 3)])
 def test_fused_ring_matches_unfused(mfhe, n, L):
     """encrypt_pair / decrypt_to_eval with the fused X-NTT * s * X-INTT row kernels (he.hip enc_ring_kernel,
     dec_ring_kernel; MFHE_OPT_HE_FUSED = 1, default) == the separate NTT / pointwise / combine kernels, bit-exact.
@@ -706,7 +716,7 @@ def test_kat7_kat8_encrypt_decrypt_reference_geometry(mfhe, pattern, tol):
     assert err < tol, err
 
 
-@pytest.mark.parametrize("n,L", [(8, 11), (64, 11), (4, 2), (16, 1)])
+@pytest.mark.parametrize("n,L", [(8, 11), (64, 11), (4, 2), (16, 1), (32, 2)])
 def test_wcrt_mfma_matches_valu_and_oracle(mfhe, orc, n, L):
     """W-CRT GEMM on i8 MFMA (digit-split exact product, wcrt_gemm.hip) == the u128 VALU kernel == oracle,
     all three layouts (matrix->poly, poly->matrix, vector), bit-exact.  Modes: 1 = LDS-staged with the
@@ -782,7 +792,7 @@ def test_encode_quantize_near_int64_limit(mfhe, small, kind):
         np.testing.assert_array_equal(outs[1][1], outs[mf][1])
 
 
-@pytest.mark.parametrize("n,log_n,L", [(8, 3, 11), (64, 6, 11), (16, 4, 3)])
+@pytest.mark.parametrize("n,log_n,L", [(8, 3, 11), (64, 6, 11), (16, 4, 3), (32, 5, 3)])
 def test_layout_transforms_vs_oracle(mfhe, orc, n, log_n, L):
     """matrix_to_poly_kernel / poly_to_matrix_kernel (HE.cu:1330-1368): matrix-major [phi][L][n*n] <->
     poly-major [phi*n][L][n], standalone, bit-exact against the oracle in both directions, and a round trip."""
@@ -833,7 +843,7 @@ def test_he_wrappers_reject_undersized_buffers(mfhe, small):
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("n,L,shard", [(4, 2, None), (8, 11, None), (4, 2, (2, 5))])
+@pytest.mark.parametrize("n,L,shard", [(4, 2, None), (8, 11, None), (4, 2, (2, 5)), (32, 2, None)])
 def test_encrypt_samplers_digitize_matches_kernels(mfhe, n, L, shard):
     """encrypt_pair draws a and e inside the factored W-CRT's digitize (MFHE_OPT_WCRT_MFMA 1, default:
     wcrt_digitize.hpp mfma_digitize_fold_kernel<D, 2> and gaussian_compact_kernel / gaussian_i8_kernel) or by
