@@ -295,6 +295,25 @@ def err(got, truth):
     return float(np.max(np.abs(np.asarray(got).astype(CLD) - truth)))
 
 
+class Report:
+    """Collects the lines of one test; fails after all of them are printed."""
+
+    def __init__(self):
+        self.bad = []
+
+    def line(self, what, kind, n, mode, e_gpu, e_ref, e_best, scale, e_ref_name="E_ref"):
+        bnd = bound(e_ref, scale)
+        ratio = e_gpu / e_ref if e_ref > 0 else float("inf") if e_gpu > 0 else 0.0
+        best = e_gpu / e_best if e_best > 0 else float("inf") if e_gpu > 0 else 0.0
+        print(f"CDFT | {what:<14s} | {kind:<7s} | n={n:<3d} | mode {mode} | E_gpu {e_gpu:.3e} | {e_ref_name} {e_ref:.3e} | "
+              f"ratio {ratio:8.3f} | E_gpu/E_best {best:9.3f} | bound {bnd:.3e} | {'ok' if e_gpu <= bnd else 'OVER'}")
+        if not e_gpu <= bnd:
+            self.bad.append((what, kind, n, mode, e_gpu, bnd))
+
+    def check(self):
+        assert not self.bad, self.bad
+
+
 @functools.lru_cache(maxsize=None)
 def _orc_w_tables(orc):
     from oracle import P

@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 
 import cdft_model as cm
-from cdft_model import PHI
+from cdft_model import PHI, Report
+from refgeom import lift, residues
 
 pytestmark = pytest.mark.gpu
 
@@ -24,25 +25,6 @@ RNS = [17592186435073, 17182765057, 17184541441]
 CONV = 1 | 4   # PHANTOM | WCRT
 DELTA = 2.0 ** 35
 MODES = (2, 3, 1, 0)
-
-
-class Report:
-    """Collects the lines of one test; fails after all of them are printed."""
-
-    def __init__(self):
-        self.bad = []
-
-    def line(self, what, kind, n, mode, e_gpu, e_ref, e_best, scale, e_ref_name="E_ref"):
-        bnd = cm.bound(e_ref, scale)
-        ratio = e_gpu / e_ref if e_ref > 0 else float("inf") if e_gpu > 0 else 0.0
-        best = e_gpu / e_best if e_best > 0 else float("inf") if e_gpu > 0 else 0.0
-        print(f"CDFT | {what:<14s} | {kind:<7s} | n={n:<3d} | mode {mode} | E_gpu {e_gpu:.3e} | {e_ref_name} {e_ref:.3e} | "
-              f"ratio {ratio:8.3f} | E_gpu/E_best {best:9.3f} | bound {bnd:.3e} | {'ok' if e_gpu <= bnd else 'OVER'}")
-        if not e_gpu <= bnd:
-            self.bad.append((what, kind, n, mode, e_gpu, bnd))
-
-    def check(self):
-        assert not self.bad, self.bad
 
 
 @pytest.fixture(scope="module")
@@ -269,18 +251,13 @@ def codec(mfhe, orc):
 
 
 def _residues(k):
-    """[512][n^2] int64 -> matrix-major [512][L][n^2] residues."""
-    q = np.array(RNS[:2], dtype=np.int64)[None, :, None]
-    return np.mod(k[:, None, :], q).astype(np.uint64).ravel()
+    """[512][n^2] int64 -> matrix-major [512][2][n^2] residues (refgeom.residues: any limb count)."""
+    return residues(k, RNS[:2])
 
 
 def _lift(res, n):
     """Matrix-major residues [512][2][n^2] -> the centred integers (int64), from limb 0 (44 bits), checked on limb 1."""
-    r = res.reshape(PHI, 2, n * n).astype(np.int64)
-    q0, q1 = RNS[0], RNS[1]
-    k = np.where(r[:, 0] > (q0 - 1) // 2, r[:, 0] - q0, r[:, 0])
-    np.testing.assert_array_equal(np.mod(k, q1), r[:, 1])
-    return k
+    return lift(res, n, RNS[:2])
 
 
 def _decode_eref(orc, h, pre, pim, k_re, k_im, n, lanes):
