@@ -206,29 +206,6 @@ int launch_ctmat_tensor(mfhe_ctx* c, CtmatArgs a, hipStream_t st) {
     return MFHE_OK;
 }
 
-// One matrix of entries as an entry point takes it.
-struct CtmatMatrix {
-    size_t rows, cols, row, col, poly;
-};
-
-// Words spanned by the matrix when no two of its entries overlap, each entry npoly polynomials of lw words: the
-// smaller of the two strides holds an entry and the larger the line of entries at the smaller (ks_span both times),
-// whichever of the two is the row stride; a stride that is never stepped (one row, one column) is free.  False when
-// entries overlap.
-static bool ctmat_span(const CtmatMatrix& x, size_t npoly, size_t lw, size_t* span) {
-    const size_t e = ks_span(npoly, x.poly, lw);
-    const size_t cols_in = ks_span(x.cols, x.col, e), rows_in = ks_span(x.rows, x.row, e);
-    if ((x.cols == 1 || x.col >= e) && (x.rows == 1 || x.row >= cols_in)) {
-        *span = ks_span(x.rows, x.row, cols_in);
-        return true;
-    }
-    if ((x.rows == 1 || x.row >= e) && (x.cols == 1 || x.col >= rows_in)) {
-        *span = ks_span(x.cols, x.col, rows_in);
-        return true;
-    }
-    return false;
-}
-
 // The operands of a matrix product as the entry points take them.
 struct CtmatOperands {
     const uint64_t *a0, *a1;
@@ -268,13 +245,6 @@ static CtmatArgs ctmat_args(const CtmatOperands& o, uint64_t* d0, uint64_t* d1, 
     a.d2_row = d2s.row; a.d2_col = d2s.col; a.d2_poly = d2s.poly;
     a.ncoeff = N; a.npoly = npoly; a.m = o.m; a.n = o.n; a.k = o.k; a.level = level;
     return a;
-}
-
-// m n npoly, the polynomials of the driver's one batch; false when it does not fit a size_t
-static bool ctmat_batch(int m, int n, size_t npoly, size_t* batch) {
-    const size_t mn = (size_t)m * (size_t)n;
-    *batch = mn * npoly;
-    return npoly == 0 || *batch / npoly == mn;
 }
 
 }  // namespace mfhe

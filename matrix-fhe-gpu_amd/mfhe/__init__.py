@@ -30,6 +30,8 @@ XCHG_ALLGATHER, XCHG_ALLTOALL = 0, 1
 BCONV_FAST, BCONV_CENTERED = 0, 1
 KS_ADD = 1                      # keyswitch: add the results to what out0 / out1 hold (relinearisation)
 CTMUL_RESCALE = 1               # ctmul: after relinearising, ModDown both outputs by limb level - 1
+PTMUL_RESCALE = 1               # ptmat: after the product, ModDown both outputs by limb level - 1
+PTMUL_ADD = 2                   # ptmat_tensor / ptmat: the outputs' present contents are added into the sums
 POLY_MONOMIAL = 0               # PolyPlan: sum a_i x^i
 POLY_CHEBYSHEV = 1              # PolyPlan: sum a_i T_i(x), slots in [-1, 1]
 SLOT_REAL = 1                   # slot_encode / slot_decode: real slots, N / 2 doubles per polynomial
@@ -172,6 +174,25 @@ _sig("mfhe_ctmat_tensor", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz
 _sig("mfhe_ctmat_reserve", [_vp, _int, _int, _sz, _int, _int, _int, _int, _int, _int])
 _sig("mfhe_ctmat_apply", [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _vp, _vp, _sz,
                           _sz, _int, _int, _int, _int, _int, _int, _vp])
+PTMUL_MAX_TERMS = 64            # ptmul_sum / ptmat_tensor / ptmat: most terms of one sum
+_sig("mfhe_ptmat_tile", [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)])
+
+
+def _ptmat_tile():
+    tm, tn = ctypes.c_int(), ctypes.c_int()
+    if lib.mfhe_ptmat_tile(ctypes.byref(tm), ctypes.byref(tn)) != OK:
+        raise ImportError("mfhe_ptmat_tile failed")
+    return tm.value, tn.value
+
+
+PTMAT_TILE = _ptmat_tile()      # ptmat_tensor: outputs one thread owns in the loaded build (kPtmatTM x kPtmatTN)
+_sig("mfhe_ptmul_sum", [_vp, _vp, _vp, _sz, _sz, _int, _vp, _sz, _sz, _int, ctypes.POINTER(_int), ctypes.POINTER(_int),
+                        _int, _int, _vp, _vp, _sz, _sz, _int, _vp])
+_sig("mfhe_ptmat_tensor", [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _sz, _sz, _sz, _vp,
+                           _vp, _sz, _sz, _sz, _sz, _int, _int, _vp])
+_sig("mfhe_ptmat_reserve", [_vp, _int, _int, _sz, _int, _int])
+_sig("mfhe_ptmat_apply", [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp, _sz, _sz, _sz, _vp,
+                          _vp, _sz, _sz, _int, _int, _vp])
 _dbl = ctypes.c_double
 LINCOMB_MAX_TERMS = 64          # ct_lincomb: most terms of one sum (a node of a PolyPlan among them)
 
@@ -1014,6 +1035,90 @@ class Context:
         check(lib.mfhe_ctmat_apply(self._h, _ptr(a0), _ptr(a1), *a, _ptr(b0), _ptr(b1), *b, m, n, k, _ptr(rlk),
                                    _ptr(out0), _ptr(out1), ost, npoly, level, key_level, alpha, special_start,
                                    nspecial, flags, _stream_ptr(stream)), "ctmat")
+        return out0, out1
+
+    # ---- plaintext x ciphertext products (include/mfhe.h): the plaintext-weighted sum, and Y = W X + B for an m x k
+    # matrix W of plaintexts and a k x n matrix X of ciphertexts in one tiled launch, with one rescale per product
+    def ptmul_sum(self, x0, x1, pt, out0, out1, term_x, term_pt, npoly, level, nsrc, npt, addend_pt=-1,
+                  src_stride=None, x_poly_stride=None, pt_stride=None, pt_poly_stride=None, out_stride=None,
+                  stream=None):
+        """(out0, out1), each [npoly][level][N] = sum_t pt[term_pt[t]] (x0, x1)[term_x[t]] + (pt[addend_pt], 0) mod
+        q_r: x0, x1 the components of nsrc ciphertexts, each [nsrc][npoly][>= level rows][N] with a source stride and a
+        poly stride; pt npt plaintexts [npt][npoly][>= level rows][N] with a pt stride and a pt poly stride, or with
+        pt_poly_stride = 0 one plaintext per index shared by the batch, [npt][>= level rows][N]; term_x, term_pt Python
+        lists of 1 .. 64 entries.  One launch."""
+        lw = level * self.N
+        pst = lw if x_poly_stride is None else x_poly_stride
+        sst = npoly * pst if src_stride is None else src_stride
+        ppst = lw if pt_poly_stride is None else pt_poly_stride
+        ptst = (npoly * ppst if ppst else lw) if pt_stride is None else pt_stride
+        ost = lw if out_stride is None else out_stride
+        if len(term_x) != len(term_pt):
+            raise ValueError("ptmul_sum: term_x and term_pt differ in length")
+        for t, what in ((x0, "x0"), (x1, "x1")):
+            self._need_polys(t, npoly, pst, level, self.N, f"ptmul_sum {what} (one source)")
+            _need(t, (nsrc - 1) * sst + (npoly - 1) * pst + lw if npoly and nsrc > 0 else 0, f"ptmul_sum {what}")
+        _need(pt, (npt - 1) * ptst + (npoly - 1) * ppst + lw if npoly and npt > 0 else 0, "ptmul_sum pt")
+        self._need_polys(out0, npoly, ost, level, self.N, "ptmul_sum out0")
+        self._need_polys(out1, npoly, ost, level, self.N, "ptmul_sum out1")
+        nt = len(term_x)
+        tx, tp = (_int * max(nt, 1))(*term_x), (_int * max(nt, 1))(*term_pt)
+        check(lib.mfhe_ptmul_sum(self._h, _ptr(x0), _ptr(x1), sst, pst, nsrc, _ptr(pt), ptst, ppst, npt, tx, tp, nt,
+                                 addend_pt, _ptr(out0), _ptr(out1), ost, npoly, level, _stream_ptr(stream)),
+              "ptmul_sum")
+        return out0, out1
+
+    def _ptmat_operands(self, w, x0, x1, bias, m, n, k, npoly, level, w_strides, x_strides, bias_strides, what):
+        """Dense strides [m][k][npoly][level][N], [k][n][npoly][level][N] and [m][n][npoly][level][N] by default, the
+        operand buffers size-checked: ((w_row, w_col, w_poly), (x_row, x_col, x_poly), (b_row, b_col, b_poly))."""
+        lw = level * self.N
+        ws = (k * npoly * lw, npoly * lw, lw) if w_strides is None else tuple(w_strides)
+        xs = (n * npoly * lw, npoly * lw, lw) if x_strides is None else tuple(x_strides)
+        bs = (n * npoly * lw, npoly * lw, lw) if bias_strides is None else tuple(bias_strides)
+        self._ctmat_need(w, m, k, npoly, level, *ws, f"{what} w")
+        for t, name in ((x0, "x0"), (x1, "x1")):
+            self._ctmat_need(t, k, n, npoly, level, *xs, f"{what} {name}")
+        if bias is not None:
+            self._ctmat_need(bias, m, n, npoly, level, *bs, f"{what} bias")
+        return ws, xs, bs
+
+    def ptmat_tensor(self, w, x0, x1, out0, out1, m, n, k, npoly, level, bias=None, flags=0, w_strides=None,
+                     x_strides=None, bias_strides=None, out_strides=None, stream=None):
+        """(out0, out1)[i][j] = sum_t w[i][t] (x0, x1)[t][j] + (bias[i][j], 0) mod q_r for the m x k matrix w of
+        plaintexts and the k x n matrix (x0, x1) of ciphertexts, npoly polynomials [level][N] per entry (and component).
+        Every *_strides is (row, col, poly) in words, dense by default; a transposed operand is the same memory with
+        row and col swapped.  w's poly stride may be 0 (one plaintext per entry for the whole batch); each of the bias'
+        three strides may be 0 (one row, one column, one polynomial of bias broadcast).  flags: PTMUL_ADD adds what the
+        outputs hold into the sums.  One launch, bit-identical to m n ptmul_sum calls."""
+        ws, xs, bs = self._ptmat_operands(w, x0, x1, bias, m, n, k, npoly, level, w_strides, x_strides, bias_strides,
+                                          "ptmat_tensor")
+        lw = level * self.N
+        o = (n * npoly * lw, npoly * lw, lw) if out_strides is None else tuple(out_strides)
+        self._ctmat_need(out0, m, n, npoly, level, *o, "ptmat_tensor out0")
+        self._ctmat_need(out1, m, n, npoly, level, *o, "ptmat_tensor out1")
+        check(lib.mfhe_ptmat_tensor(self._h, _ptr(w), *ws, _ptr(x0), _ptr(x1), *xs, m, n, k, _ptr(bias), *bs,
+                                    _ptr(out0), _ptr(out1), *o, npoly, level, flags, _stream_ptr(stream)),
+              "ptmat_tensor")
+        return out0, out1
+
+    def ptmat_reserve(self, m, n, npoly, level, flags=0):
+        """Grow the workspace and build the rescale's table (with PTMUL_RESCALE; nothing is needed without): ptmat then
+        allocates nothing and copies nothing to the device."""
+        check(lib.mfhe_ptmat_reserve(self._h, m, n, npoly, level, flags), "ptmat_reserve")
+
+    def ptmat(self, w, x0, x1, out0, out1, m, n, k, npoly, level, bias=None, flags=0, w_strides=None, x_strides=None,
+              bias_strides=None, out_stride=None, stream=None):
+        """(out0, out1), each [m][n][npoly][level][N] at one poly stride = w (x0, x1) + (bias, 0) as ptmat_tensor
+        computes it.  flags: PTMUL_ADD as there; PTMUL_RESCALE also divides by q_(level-1) in one ModDown over all
+        m n npoly polynomials, and rows [0, level - 1) of the outputs then hold the result at level - 1."""
+        ws, xs, bs = self._ptmat_operands(w, x0, x1, bias, m, n, k, npoly, level, w_strides, x_strides, bias_strides,
+                                          "ptmat")
+        ost = level * self.N if out_stride is None else out_stride
+        batch = max(m, 0) * max(n, 0) * npoly
+        self._need_polys(out0, batch, ost, level, self.N, "ptmat out0")
+        self._need_polys(out1, batch, ost, level, self.N, "ptmat out1")
+        check(lib.mfhe_ptmat_apply(self._h, _ptr(w), *ws, _ptr(x0), _ptr(x1), *xs, m, n, k, _ptr(bias), *bs,
+                                   _ptr(out0), _ptr(out1), ost, npoly, level, flags, _stream_ptr(stream)), "ptmat")
         return out0, out1
 
     # ---- encrypted polynomial evaluation (include/mfhe.h): scalar sums of ciphertexts and the plans built on them
